@@ -7,17 +7,25 @@ reference-attention banks, then window accumulate + CFG combine + DDIM update.  
 All inputs are resident in HBM before the timed region.  N GPUs = N independent clips (clip-parallel, no collective in
 the loop), so `value` is the aggregate over ranks and scaling is "weak".
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--full-cpu-baseline] [--no-extras]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--full-cpu-baseline] [--no-extras] [--no-calib]]
 
 With --gpus N > 1 and no RANK in the environment, bench.py starts `python -m torch.distributed.run --nproc-per-node N` on
 itself as a CHILD process (before anything touches the GPU) and exits with its return code; under torch.distributed.run it
 reads RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as usual.
 
-Besides the contract's line (metric / value / roofline / cpu_baseline) rank 0 at N = 1 reports, timed OUTSIDE the step loop
+A plain run sets up, warms up, times the K steps and prints the contract's line (metric / value / ms_per_step / roofline; the
+roofline's traffic and matrix-pipe figures are read from the committed profiles, not measured).  --dump-outputs DIR then writes
+the latents the last timed step returned, as float32 DIR/latents.npy (DIR/latents_rank<r>.npy on rank r > 0): the inputs and
+weights are pure functions of their names, so two builds run with the same arguments can be compared output for output.
+
+--full adds everything else.  Rank 0 at N = 1 then also reports `cpu_baseline`, `box_calib` and, timed OUTSIDE the step loop
 ("exclude prologue + VAE, report them separately"): `vae_decode` (ms per 512x512 frame and its MFMA roofline
 fraction at 2.51 TFLOP per frame), `prologue_ms` (CLIP ViT-L/14 + VAE encode + ReferenceNet + PoseGuider + bank projection,
-once per clip), `max_abs_delta_vs_cpu` (bf16 HIP forward against the CPU fp32 oracle on the cpu_baseline's sample) and
-`roofline_kernels` (live HIP-event timings of the step's heaviest kernels at their in-step shapes).
+once per clip), `max_abs_delta_vs_cpu` (bf16 HIP forward against the CPU fp32 oracle on the cpu_baseline's sample),
+`roofline_kernels` (live HIP-event timings of the step's heaviest kernels at their in-step shapes) and the other geometries
+(`config5_ms_per_step`, `ctx12_ms_per_window`, `smga_ms_per_slice`).  --no-cpu-baseline / --no-extras / --no-calib drop
+single legs of a --full run.
 """
 import argparse
 import json
@@ -67,16 +75,23 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the latents of the last one as float32 DIR/latents.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, box_calib, the per-kernel rooflines, VAE / prologue and the other geometries")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle leg")
     ap.add_argument("--full-cpu-baseline", action="store_true",
-                    help="time one FULL 24-frame CFG forward of the oracle on the host (minutes); the default on hosts with >= 64 cores")
+                    help="(--full) time one FULL 24-frame CFG forward of the oracle on the host (minutes); the default on hosts with >= 64 usable cores")
     ap.add_argument("--sample-cpu-baseline", action="store_true",
-                    help="time the 2-of-24-frame sample of the oracle only (the default on hosts with < 64 cores)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the VAE / prologue / per-kernel legs")
-    ap.add_argument("--no-calib", action="store_true", help="skip box_calib (profiled runs: its kernels are not part of the step)")
+                    help="(--full) time the 2-of-24-frame sample of the oracle only (the default on hosts with < 64 usable cores)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the VAE / prologue / per-kernel legs")
+    ap.add_argument("--no-calib", action="store_true", help="(--full) skip box_calib (profiled runs: its kernels are not part of the step)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--master-port", type=int, default=0)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def self_launch(a):
@@ -125,7 +140,7 @@ def cpu_baseline(sd_cpu, frames_sample=2):
     frames_sample = 24 (--full-cpu-baseline) it is one measured step.  Returns (record, inputs, oracle output)."""
     import torch
     from oracle import unet3d_ref as R
-    cores = max(1, (os.cpu_count() or 2) // 2)
+    cores = max(1, min((os.cpu_count() or 2) // 2, _usable_cores()))
     torch.set_num_threads(cores)
     inp = build_inputs("cpu", frames=frames_sample, tag="bench.cpu")
     sample, ehs, audio, pose, full, face, lips = operator_args(inp, "cpu")
@@ -190,6 +205,22 @@ def _cpu_name():
     except OSError:
         pass
     return "unknown"
+
+
+def _usable_cores():
+    """Host CPUs this process may use: os.cpu_count() is the whole machine's, the affinity mask, a cgroup CPU quota and OMP_NUM_THREADS
+    can each allow fewer (a thread pool sized past them only slows the oracle down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(1, n)
 
 
 def _time_ms(fn, reps=20, warm=3):
@@ -475,7 +506,7 @@ def main():
     unet.load_state_dict(sd)
     unet.enable_gradient_checkpointing()                      # script semantics: motion_scale applied
     sd_cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         sd_cpu = {k: v.cpu() for k, v in sd.items()}
     del sd
     torch.cuda.empty_cache()
@@ -518,6 +549,11 @@ def main():
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if a.dump_outputs:
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "latents.npy" if rank == 0 else f"latents_rank{rank}.npy"),
+                out.detach().float().cpu().numpy())
 
     if rank == 0:
         per_gpu = a.steps / elapsed
@@ -545,14 +581,15 @@ def main():
                                  f"kernel cycles) over the step's kernels from {busy_src} -- both are committed rocprofv3 PMC passes of this "
                                  f"command at --steps 3 --warmup 1 (per-step = total / 4), not measurements of this {a.steps}-step run"},
         }
-        if not a.no_calib:
+        if a.full and not a.no_calib:
             res["box_calib"] = box_calib(dev, dtype)
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             res["roofline_kernels"] = kernel_rooflines(unet, dev)
             res.update(extras(pipe, unet, dev, dtype))
         if sd_cpu is not None:
-            # a measured full step (about 160 s on the GPU box's 128 host cores) is what the default line carries; small hosts keep the sample
-            full_cpu = a.full_cpu_baseline or (not a.sample_cpu_baseline and (os.cpu_count() or 1) >= 64)
+            # a measured full step (about 160 s on 64 threads of a 128-core host) is what a --full line carries where 64 cores are usable;
+            # smaller hosts keep the sample
+            full_cpu = a.full_cpu_baseline or (not a.sample_cpu_baseline and _usable_cores() >= 64)
             rec, cinp, cout = cpu_baseline(sd_cpu, FRAMES if full_cpu else 2)
             res["cpu_baseline"] = rec
             del sd_cpu

@@ -680,3 +680,21 @@ print(json.dumps(seen))
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[cmd.index("--master-port") + 1].isdigit()
     i = cmd.index(os.path.join(root, "bench.py"))
     assert cmd[i + 1:] == ["--gpus", "8", "--steps", "5", "--warmup", "2"]
+
+
+def test_bench_options_plain_run_by_default(monkeypatch):
+    """--full (CPU baseline, calibration, per-kernel and other-geometry legs) is off unless asked for; --dump-outputs takes a folder;
+    --steps below 1 is refused; the CPU leg's thread count stays within the CPUs this process may use."""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse_args()
+    assert (a.gpus, a.steps, a.warmup, a.full, a.dump_outputs) == (1, 7, 3, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir"])
+    a = bench.parse_args()
+    assert a.full and a.dump_outputs == "out_dir"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    monkeypatch.setenv("OMP_NUM_THREADS", "3")
+    assert 1 <= bench._usable_cores() <= 3

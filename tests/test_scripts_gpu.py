@@ -1,6 +1,6 @@
 """The counterpart scripts of SURVEY 8c end to end on the device, at BASELINE config-1 size (64x64 px, 8 frames, few DDIM steps):
 scripts/pose2vid.py --synthetic and scripts/audio2vid.py --synthetic (BASELINE config 3: SMGA audio->pose chained into Stage 2,
-device-side conditioning, uint8 output path)."""
+device-side conditioning, uint8 output path); and a plain bench.py run with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -18,6 +18,20 @@ def _run(script, *args):
                        timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def test_bench_plain_run_prints_the_line_and_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the contract's line and none of the --full legs; --dump-outputs writes the latents the last timed step
+    returned, as float32."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs",
+                        str(tmp_path)], capture_output=True, text=True, cwd=ROOT, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    rec = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["unit"] == "steps/s" and rec["higher_is_better"] is True and rec["dtype"] == "bf16"
+    assert rec["ms_per_step"] > 0 and abs(rec["value"] * rec["ms_per_step"] - 1e3) < 1e-6
+    assert not {"cpu_baseline", "box_calib", "roofline_kernels", "vae_decode", "prologue_ms", "max_abs_delta_vs_cpu"} & set(rec)
+    lat = np.load(tmp_path / "latents.npy")
+    assert lat.shape == (1, 4, 24, 64, 64) and lat.dtype == np.float32 and np.isfinite(lat).all() and lat.std() > 0
 
 
 def test_audio2vid_synthetic_chain_smga_into_stage2(tmp_path):
