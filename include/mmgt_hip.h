@@ -255,6 +255,18 @@ int mmgt_channel_norm_gelu(const void* x, const float* gamma, const float* beta,
                            void* stream);
 int mmgt_lerp_rows(const void* x, void* out, int rows_in, int rows_out, int C, int dtype, void* stream);
 
+/* WavLM self-attention with the gated relative-position bias (csrc/wavlm.hip), per (batch b, head h, query i):
+ *   o[b][i][h] = softmax_j(q_i . k_j * scale + gate[b][h][i] * tab[h][j - i + T - 1]) V,   head_dim 64, nq = nk = T in 1 .. 4096,
+ *   gate = a (c grep_a[h] - 1) + 2 with (a, c) = sigmoid of the two group-of-4 sums of grep_w (8 x 64, fp32) . x[b][i][h*64 .. +63] + grep_b,
+ * computed in the kernel from x, the layer input after self_attn_layer_norm (rows of stride x_ts, batch stride x_bs, in `dtype`).
+ * tab: (heads, 2T - 1) fp32, the raw bias of layer 0 (compute_bias) by offset j - i.  q/k/v/o rows are strided like mmgt_attention's
+ * (element strides: batch *_bs, row *_ts; head h at column h*64), so the q|k|v GEMM output is read in place.  Softmax and gate in fp32.
+ * Replaces: the reference's data/wavlm/modules_wavlm.py:504-540 (gate + position bias + F.multi_head_attention_forward's softmax(QK^T + mask) V)
+ * and :444-455 per layer (the bias of WavLM.py:596-601, passed from layer 0 to all layers). */
+int mmgt_relpos_attention(const void* q, long q_bs, long q_ts, const void* k, long k_bs, long k_ts, const void* v, long v_bs, long v_ts,
+                          void* o, long o_bs, long o_ts, const void* x, long x_bs, long x_ts, const float* grep_w, const float* grep_b,
+                          const float* grep_a, const float* tab, int batch, int heads, int hd, int T, float scale, int dtype, void* stream);
+
 /* Elementwise x -> silu(x) (time embedding activation, resnet.py:226) over n elements. */
 int mmgt_silu(const void* x, void* out, long n, int dtype, void* stream);
 

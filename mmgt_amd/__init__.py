@@ -5,3 +5,12 @@ C ABI declared in include/mmgt_hip.h); the Python here mirrors the reference's o
 (src/models/unet_3d.py, src/pipelines/pipeline_pose2vid_long.py) and does plumbing only.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # WavLM / WavLMConfig are exported lazily: `import mmgt_amd` stays as light as it was, and only a caller that asks for them
+    # imports mmgt_amd.wavlm (and torch) -- `from mmgt_amd import WavLM` works as for any other export
+    if name in ("WavLM", "WavLMConfig"):
+        from . import wavlm
+        return getattr(wavlm, name)
+    raise AttributeError(f"module 'mmgt_amd' has no attribute {name!r}")

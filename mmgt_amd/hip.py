@@ -87,6 +87,9 @@ _SIGS = {
                                      c_void_p]),
     "mmgt_channel_norm_gelu": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
     "mmgt_lerp_rows": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_relpos_attention": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long, c_void_p, c_long, c_long,
+                                      c_void_p, c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                      c_int, c_void_p]),
     "mmgt_silu": (c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p]),
     "mmgt_cfg_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_float, c_void_p]),
@@ -674,6 +677,20 @@ def attention(q, k, v, out, *, batch, heads, hd, nq, nk, scale, q_str, k_str, v_
                                 _ptr(v2), k2_str[0], k2_str[1], v2_str[0], v2_str[1], k2_bdiv, nk2, seg2_first_batch,
                                 batch, heads, hd, nq, nk, scale, int(v_transposed), dtype_code(q.dtype), _stream()),
            "mmgt_attention")
+    return out
+
+
+def relpos_attention(q, k, v, out, x, grep_w, grep_b, grep_a, tab, *, batch, heads, T, scale, q_str, k_str, v_str, o_str, x_str, hd=64):
+    """WavLM's attention with the gated relative-position bias (see include/mmgt_hip.h).  *_str = (batch stride, row stride) in
+    elements; head h at column h * 64.  x: the LayerNorm output the gate is computed from; grep_w (8, 64), grep_b (8,), grep_a (heads,),
+    tab (heads, 2T - 1): fp32."""
+    _dev(q, k, v, out, x, grep_w, grep_b, grep_a, tab)
+    assert q.dtype == k.dtype == v.dtype == out.dtype == x.dtype
+    assert tuple(tab.shape) == (heads, 2 * T - 1) and grep_w.numel() == 8 * 64 and grep_b.numel() == 8 and grep_a.numel() == heads
+    _check(lib().mmgt_relpos_attention(_ptr(q), q_str[0], q_str[1], _ptr(k), k_str[0], k_str[1], _ptr(v), v_str[0], v_str[1],
+                                       _ptr(out), o_str[0], o_str[1], _ptr(x), x_str[0], x_str[1], _ptr(_f32(grep_w, "grep_w")),
+                                       _ptr(_f32(grep_b, "grep_b")), _ptr(_f32(grep_a, "grep_a")), _ptr(_f32(tab, "tab")), batch, heads, hd,
+                                       T, scale, dtype_code(q.dtype), _stream()), "mmgt_relpos_attention")
     return out
 
 

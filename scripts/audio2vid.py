@@ -17,8 +17,10 @@ The chain is the reference's (line numbers of its scripts/audio2vid.py):
   5. Pose2VideoPipeline (:484-498), frames converted to uint8 on the device, written as .npy / .gif.
 
 --synthetic: random-init weights of the reference architectures (no checkpoints ship with the reference), a synthetic 16-kHz
-waveform for the wav2vec2 leg, and synthetic WavLM + baseline features for SMGA (WavLM / librosa extraction and vocal separation are
-host-side and out of scope).  Without --synthetic the script stops with a clear message: it would need those extractors, cv2 and PyAV.
+waveform for the wav2vec2 leg, and synthetic WavLM + baseline features for SMGA (librosa extraction and vocal separation are host-side
+and out of scope).  --wavlm {random,PATH} with --audio_path replaces the WavLM stand-in by real WavLM-Large features of the audio
+(mmgt_amd.wavlm on HIP: the reference's slicing, scripts/audio2vid.py:299-315, and extract_wo_init); --baseline_feats supplies the 35
+librosa columns.  Without --synthetic the script stops with a clear message: it would need those extractors, cv2 and PyAV.
 """
 import argparse
 import json
@@ -55,6 +57,13 @@ def parse_args():
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--format", default="npy", choices=["npy", "gif"])
+    p.add_argument("--wavlm", default="off", metavar="{off,random,PATH}",
+                   help="WavLM-Large features of --audio_path as columns 0:1024 of the SMGA conditioning: off (hash-seeded stand-in, the default), "
+                        "random (hash-seeded Large weights) or the path of a WavLM-Large.pt checkpoint")
+    p.add_argument("--baseline_feats", type=str, default=None,
+                   help="(n_slices, 80, 35) .npy of the reference's librosa baseline features for columns 1024:1059 (librosa is not part of "
+                        "this build; without it those columns keep the hash-seeded stand-in)")
+    p.add_argument("--save_cond", type=str, default=None, help="write the (n_slices, 80, 1059) SMGA conditioning handed to the sampler to this .npy")
     return p.parse_args()
 
 
@@ -133,6 +142,38 @@ def main():
     # ---- 1. SMGA: audio -> key points, one 80-frame slice per 3.2 s (:300-348)
     n_slices = max(1, -(-a.L // 80))
     cond_list = hash_uniform("a2v.wavlm+baseline", (n_slices, 80, 1059), 1.0)          # WavLM (1024) + baseline (35) features per frame
+    extra = {}
+    if a.wavlm != "off":                                                                # :299-315: WavLM features of the audio slices
+        from mmgt_amd.wavlm import WavLM, WavLMConfig, audio_slices, wavlm_spec
+        if not a.audio_path:
+            raise SystemExit("audio2vid: --wavlm needs --audio_path (a 16-kHz PCM .wav)")
+        torch.cuda.synchronize()
+        t0 = time.time()
+        slices = audio_slices(read_wav_16k(a.audio_path))
+        if slices.shape[0] < n_slices or slices.shape[1] != 51200:
+            raise SystemExit(f"audio2vid: {a.audio_path} gives {slices.shape[0]} slice(s) of {slices.shape[1]} samples; -L {a.L} needs "
+                             f"{n_slices} full 3.2-s slices (the reference skips the first window of clips longer than 3.3 s)")
+        if a.wavlm == "random":
+            wavlm = WavLM(WavLMConfig(), device=dev, dtype=dtype)
+            wavlm.load_state_dict(synth_state_dict(wavlm_spec(), prefix="wavlm.", device=dev))
+        else:
+            wavlm = WavLM.from_checkpoint(a.wavlm, device=dev, dtype=dtype)
+        cond_list[:, :, :1024] = wavlm.slice_features(slices.to(dev)).cpu()[:n_slices]                  # all slices in one call
+        del wavlm
+        torch.cuda.synchronize()
+        extra["wavlm"] = a.wavlm
+        extra["wavlm_slices"] = int(slices.shape[0])
+        extra["wavlm_s"] = round(time.time() - t0, 3)
+        if a.baseline_feats:
+            bf = torch.from_numpy(np.load(a.baseline_feats)).float()
+            if tuple(bf.shape) != (n_slices, 80, 35):
+                raise SystemExit(f"audio2vid: --baseline_feats holds {tuple(bf.shape)}, expected {(n_slices, 80, 35)}")
+            cond_list[:, :, 1024:] = bf
+        extra["baseline_feats"] = a.baseline_feats or "hash"
+    elif a.baseline_feats:
+        raise SystemExit("audio2vid: --baseline_feats goes with --wavlm random|PATH")
+    if a.save_cond:
+        np.save(a.save_cond, cond_list.numpy())
     init_feature = hash_uniform("a2v.init_pose", (1, 402), 0.8)                         # process_reference_image + mask_leg (:319-321)
     gen = torch.Generator(device=dev).manual_seed(a.seed)
     torch.cuda.synchronize()
@@ -189,7 +230,7 @@ def main():
     save_videos_grid(v, path, n_rows=1, fps=a.fps or 25)
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
                       "dtype": a.dtype, "keypoints_finite": bool(np.isfinite(kps).all()),
-                      "mask_levels": [list(m.shape) for m in face], **timing}))
+                      "mask_levels": [list(m.shape) for m in face], **timing, **extra}))
 
 
 if __name__ == "__main__":
