@@ -378,6 +378,25 @@ int mmgt_window_stack(const float* x, float* out, int frames, long D, int half, 
  * (x / 2 + 0.5).clamp(0, 1) (pipeline_pose2vid_long.py:121-123) fused with save_videos_grid's (x * 255).astype(uint8)
  * (src/utils/util.py:148-160). */
 int mmgt_frames_to_u8(const void* x, unsigned char* out, long npix, int cpad, float scale, float shift, int dtype, void* stream);
+/* ---- Motion-JPEG output path (csrc/mjpeg.hip, mmgt_amd/video_out.py): baseline sequential JPEG (ITU T.81, JFIF 1.01) of device-resident frames.
+ * subsampling is 420 (MCU 16 x 16, blocks Y00 Y01 Y10 Y11 Cb Cr) or 444 (MCU 8 x 8, blocks Y Cb Cr); mcu_rows / mcu_cols = ceil(H or W / MCU side);
+ * quality 1 .. 100 scales the Annex K tables by the IJG rule.  Every buffer but qtables' is a device pointer.
+ * dct_quant: frames (n, H, W, 3) u8 RGB -> coef (n, mcu_rows, mcu_cols, blocks per MCU, 64) int16 in zigzag order, DC in [-1024, 1023], AC in
+ * [-1023, 1023]; H and W need not be MCU multiples (edge replication). */
+int mmgt_jpeg_dct_quant(const unsigned char* frames, short* coef, int n, int H, int W, int subsampling, int quality, void* stream);
+/* coef -> one byte-aligned, 0xFF-stuffed entropy-coded segment per (frame, MCU row) with the DC predictors reset (restart interval = one MCU
+ * row, Annex K Huffman tables): segment s at segs + s * seg_stride, its byte count in sizes[s].  seg_stride >= segment_stride(W): the bound no
+ * input can exceed. */
+int mmgt_jpeg_entropy(const short* coef, unsigned char* segs, int* sizes, int n, int H, int W, int subsampling, long seg_stride, void* stream);
+int mmgt_jpeg_segment_stride(int W, int subsampling, long* stride);
+/* offsets[s] = sum over s' < s of (sizes[s'] + 2), offsets[nseg] = the total: where compact puts segment s and its marker. */
+int mmgt_jpeg_scan(const int* sizes, long long* offsets, int nseg, void* stream);
+/* out[offsets[s] ...] = segment s followed by RSTm (m = MCU row & 7) or, after the last MCU row of a frame, EOI: frame f's scan data with all its
+ * markers is out[offsets[f * mcu_rows] : offsets[(f + 1) * mcu_rows]].  out_bytes = offsets[nseg]. */
+int mmgt_jpeg_compact(const unsigned char* segs, long seg_stride, const int* sizes, const long long* offsets, unsigned char* out, long long out_bytes,
+                      int nseg, int mcu_rows, void* stream);
+/* Host: the luminance and chrominance quantiser tables of `quality` in zigzag order (the body of two DQT segments), 128 bytes. */
+int mmgt_jpeg_qtables(int quality, unsigned char* zigzag128);
 /* SMGA key points -> the four frame streams of Stage 2, drawn on the device: kp (frames, 134, 3) fp32 = SMGA's normalised
  * (x, y, score) features.  Replaces data/extract_movment_mask_all.py:319-321 `pose_vid_generator` (denormalize :128-132, mask_leg :66-89,
  * process_keypoints :98-119), src/dwpose/__init__.py:220-283 `DWposeDetector_movment_mask.__call__` with draw_pose / draw_pose_mask_head /

@@ -105,6 +105,12 @@ _SIGS = {
     "mmgt_resample_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "mmgt_window_stack": (c_int, [c_void_p, c_void_p, c_int, c_long, c_int, c_void_p]),
     "mmgt_frames_to_u8": (c_int, [c_void_p, c_void_p, c_long, c_int, c_float, c_float, c_int, c_void_p]),
+    "mmgt_jpeg_dct_quant": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_jpeg_entropy": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p]),
+    "mmgt_jpeg_segment_stride": (c_int, [c_int, c_int, ctypes.POINTER(c_long)]),
+    "mmgt_jpeg_scan": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "mmgt_jpeg_compact": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
+    "mmgt_jpeg_qtables": (c_int, [c_int, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
@@ -940,6 +946,80 @@ def frames_to_u8(x, scale=0.5, shift=0.5):
                                    dtype_code(x.dtype), _stream()), "mmgt_frames_to_u8")
     return out
 
+
+# ------------------------------------------------------------------------------------------------------------ Motion-JPEG (csrc/mjpeg.hip)
+
+JPEG_SUBSAMPLING = {"4:2:0": 420, "4:4:4": 444}
+
+
+def _jpeg_ss(subsampling):
+    """"4:2:0" / "4:4:4" -> the library's code; anything else goes through as an int (or 0) so that the library refuses it with its message."""
+    if subsampling in JPEG_SUBSAMPLING:
+        return JPEG_SUBSAMPLING[subsampling]
+    return subsampling if isinstance(subsampling, int) else 0
+
+
+def jpeg_geometry(H, W, subsampling):
+    """(mcu_rows, mcu_cols, blocks per MCU) of an H x W frame."""
+    side, bpm = (16, 6) if _jpeg_ss(subsampling) == 420 else (8, 3)
+    return -(-H // side), -(-W // side), bpm
+
+
+def jpeg_qtables(quality):
+    """The (luminance, chrominance) quantiser tables of `quality` as 2 x 64 bytes in zigzag order: what the kernel divides by."""
+    buf = ctypes.create_string_buffer(128)
+    _check(lib().mmgt_jpeg_qtables(int(quality), buf), "mmgt_jpeg_qtables")
+    return buf.raw[:64], buf.raw[64:]
+
+
+def jpeg_segment_stride(W, subsampling):
+    """Bytes that one MCU row's entropy-coded segment cannot exceed, whatever the input (csrc/mjpeg.hip states the bound)."""
+    v = c_long(0)
+    _check(lib().mmgt_jpeg_segment_stride(int(W), _jpeg_ss(subsampling), ctypes.byref(v)), "mmgt_jpeg_segment_stride")
+    return v.value
+
+
+def jpeg_dct_quant(frames, quality=90, subsampling="4:2:0"):
+    """(n, H, W, 3) uint8 RGB -> (n, mcu_rows, mcu_cols, blocks per MCU, 64) int16 quantised DCT coefficients in zigzag order."""
+    _dev(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise RuntimeError("jpeg_dct_quant: frames must be contiguous uint8 (n, H, W, 3)")
+    n, H, W, _ = frames.shape
+    out = torch.empty((n,) + jpeg_geometry(H, W, subsampling) + (64,), device=frames.device, dtype=torch.int16)
+    _check(lib().mmgt_jpeg_dct_quant(_ptr(frames), _ptr(out), n, H, W, _jpeg_ss(subsampling), int(quality), _stream()), "mmgt_jpeg_dct_quant")
+    return out
+
+
+def jpeg_entropy(coef, H, W, subsampling="4:2:0", out=None):
+    """Coefficients of jpeg_dct_quant -> (segs (n * mcu_rows, stride) uint8, sizes (n * mcu_rows,) int32): one entropy-coded segment per
+    (frame, MCU row); only the first sizes[s] bytes of a row of `segs` are written.  `out` = (segs, sizes) to write into."""
+    _dev(coef)
+    assert coef.dtype == torch.int16 and coef.dim() == 5 and coef.is_contiguous()
+    n, rows = coef.shape[0], coef.shape[1]
+    stride = jpeg_segment_stride(W, subsampling)
+    if out is None:
+        out = (torch.empty((n * rows, stride), device=coef.device, dtype=torch.uint8),
+               torch.empty((n * rows,), device=coef.device, dtype=torch.int32))
+    segs, sizes = out
+    assert segs.shape == (n * rows, stride) and segs.dtype == torch.uint8 and segs.is_contiguous() and sizes.shape == (n * rows,)
+    assert tuple(coef.shape[1:4]) == jpeg_geometry(H, W, subsampling)
+    _check(lib().mmgt_jpeg_entropy(_ptr(coef), _ptr(segs), _ptr(sizes), n, H, W, _jpeg_ss(subsampling), stride, _stream()), "mmgt_jpeg_entropy")
+    return segs, sizes
+
+
+def jpeg_compact(segs, sizes, mcu_rows):
+    """-> (data uint8 on the device, offsets int64 (nseg + 1,) on the HOST): frame f's scan data with its RSTm / EOI markers is
+    data[offsets[f * mcu_rows]:offsets[(f + 1) * mcu_rows]].  One small D2H copy (the offsets) sizes the buffer."""
+    _dev(segs, sizes)
+    nseg = sizes.shape[0]
+    offsets = torch.empty((nseg + 1,), device=segs.device, dtype=torch.int64)
+    _check(lib().mmgt_jpeg_scan(_ptr(sizes), _ptr(offsets), nseg, _stream()), "mmgt_jpeg_scan")
+    host = offsets.cpu()
+    total = int(host[-1])
+    data = torch.empty((total,), device=segs.device, dtype=torch.uint8)
+    _check(lib().mmgt_jpeg_compact(_ptr(segs), segs.shape[1], _ptr(sizes), _ptr(offsets), _ptr(data), total, nseg, int(mcu_rows), _stream()),
+           "mmgt_jpeg_compact")
+    return data, host
 
 
 def dwpose_draw(kp, H=512, W=512):

@@ -4,7 +4,8 @@ device (mmgt_amd/conditioning.py) instead of cv2 / PIL on the host.
 
   read_frames        frames of a clip as PIL images (reference: src/utils/util.py read_frames, PyAV).  Containers that need a video
                      decoder (.mp4, .avi, .mov, .mkv, .webm) raise: PyAV / cv2 are not part of this build; a directory of images,
-                     a .npy stack or an animated .gif / .png / .webp is read instead.
+                     a .npy stack or an animated .gif / .png / .webp is read instead.  The one exception is an .avi whose video stream
+                     is Motion-JPEG (what mmgt_amd.video_out.write_avi writes): its frames are JPEG files, which PIL decodes.
   pose_tensor        transforms.Resize((H, W)) + ToTensor of the pose frames -> (1, 3, L, H, W) float in [0, 1]
                      (scripts/pose2vid.py:231-236)
   motion_masks       face / lips / hands mask frames -> blur_mask (resize 64 x 64, Gaussian 31 / 21 / 21, min-max normalise) ->
@@ -23,9 +24,45 @@ VIDEO_CONTAINERS = {".mp4", ".avi", ".mov", ".mkv", ".webm", ".m4v"}
 IMAGE_SUFFIXES = {".png", ".jpg", ".jpeg", ".bmp", ".webp", ".tif", ".tiff"}
 
 
+def _riff_chunks(buf, start, end):
+    """(fourcc, body offset, body size) of the chunks in buf[start:end]; chunks are padded to even length."""
+    pos = start
+    while pos + 8 <= end:
+        size = int.from_bytes(buf[pos + 4:pos + 8], "little")
+        yield buf[pos:pos + 4], pos + 8, size
+        pos += 8 + size + (size & 1)
+
+
+def mjpeg_avi_frames(path, limit: Optional[int] = None):
+    """The JPEG files of the '00dc' chunks of a RIFF AVI whose first video stream is MJPG, in file order; None if `path` is not such a file
+    (another container, another codec)."""
+    with open(path, "rb") as fh:
+        buf = fh.read()
+    if len(buf) < 12 or buf[:4] != b"RIFF" or buf[8:12] != b"AVI ":
+        return None
+    codec, frames = None, []
+    for cc, off, size in _riff_chunks(buf, 12, len(buf)):
+        if cc != b"LIST":
+            continue
+        kind = buf[off:off + 4]
+        if kind == b"hdrl":
+            for cc2, off2, size2 in _riff_chunks(buf, off + 4, off + size):
+                if cc2 == b"LIST" and buf[off2:off2 + 4] == b"strl" and codec is None:
+                    for cc3, off3, size3 in _riff_chunks(buf, off2 + 4, off2 + size2):
+                        if cc3 == b"strh" and buf[off3:off3 + 4] == b"vids":
+                            codec = buf[off3 + 4:off3 + 8]
+        elif kind == b"movi":
+            if codec is None or codec.upper() != b"MJPG":
+                return None
+            for cc2, off2, size2 in _riff_chunks(buf, off + 4, off + size):
+                if cc2 == b"00dc" and (limit is None or len(frames) < limit):
+                    frames.append(buf[off2:off2 + size2])
+    return frames if codec is not None and codec.upper() == b"MJPG" else None
+
+
 def read_frames(path, limit: Optional[int] = None) -> list:
     """PIL frames of `path`: a directory of images (sorted by name), a .npy stack (L, H, W[, C]) uint8, an animated image
-    (.gif / .png / .webp) or one still image."""
+    (.gif / .png / .webp), one still image, or a Motion-JPEG .avi."""
     from PIL import Image, ImageSequence
     p = Path(path)
     if not p.exists():
@@ -36,6 +73,11 @@ def read_frames(path, limit: Optional[int] = None) -> list:
             raise RuntimeError(f"read_frames: no image files ({', '.join(sorted(IMAGE_SUFFIXES))}) in {p}")
         return [Image.open(f).copy() for f in (files if limit is None else files[:limit])]
     suf = p.suffix.lower()
+    if suf == ".avi":
+        import io
+        jpegs = mjpeg_avi_frames(p, limit)
+        if jpegs is not None:
+            return [Image.open(io.BytesIO(j)).convert("RGB") for j in jpegs]
     if suf in VIDEO_CONTAINERS:
         raise RuntimeError(f"read_frames: {p.name} needs a video decoder (PyAV / cv2: src/utils/util.py read_frames), which this build "
                            f"does not include -- extract the frames into a directory of images or a .npy stack and pass that instead")

@@ -9,6 +9,7 @@ Extensions through **kwargs (allowed by the reference signature, :365): `latents
 `clip_image_embeds=` / `ref_image_latents=` / `reference_banks=` / `pose_features=` (hand over prologue results when the module
 is None), `decode=False`, `window_group=` / `cfg_split=` (window-parallel sampling of one long video over several GPUs).
 `output_type="uint8"` returns the frames as uint8 (b, f, H, W, 3), converted on the device (what save_videos_grid writes).
+`output_type="jpeg"` (with `jpeg_quality=`, `jpeg_subsampling=`) returns one JPEG file (bytes) per frame, encoded on the device.
 """
 import math
 from dataclasses import dataclass
@@ -96,6 +97,25 @@ class Pose2VideoPipeline:
         part = self.vae.decode_video(latents[:, :, idx])
         parts = parallel.allgather_window_predictions(part, group)
         return torch.cat(parts, dim=2)[:, :, :f].cpu().float().numpy()
+
+    def decode_latents_jpeg(self, latents, window_group=None, quality=90, subsampling="4:2:0"):
+        """The frames of ONE clip as JPEG files (AutoencoderKL.decode_video_jpeg): a list of f byte strings.  With a window_group each rank
+        decodes and encodes its own contiguous run of frames and the byte strings are gathered, so every rank returns the whole list."""
+        if self.vae is None:
+            raise RuntimeError("decode_latents needs a VAE (pass decode=False to get latents)")
+        if latents.shape[0] != 1:
+            raise ValueError(f'output_type="jpeg" returns one list of frames: batch 1 only, got batch {latents.shape[0]}')
+        if window_group is None:
+            return self.vae.decode_video_jpeg(latents, quality, subsampling)
+        group = None if window_group is True else window_group
+        world, rank = parallel.dist.get_world_size(group), parallel.dist.get_rank(group)
+        f = latents.shape[2]
+        per = (f + world - 1) // world
+        lo, hi = min(rank * per, f), min((rank + 1) * per, f)
+        mine = self.vae.decode_video_jpeg(latents[:, :, lo:hi], quality, subsampling) if hi > lo else []
+        parts = [None] * world
+        parallel.dist.all_gather_object(parts, mine, group=group)
+        return [j for part in parts for j in part]
 
     def interpolate_latents(self, latents, interpolation_factor, device=None):
         """pipeline_pose2vid_long.py:292-335 (no-op below factor 2): all pairs and rates in one batched expression."""
@@ -301,6 +321,10 @@ class Pose2VideoPipeline:
             latents = self.interpolate_latents(latents, interpolation_factor, dev)
         if not kwargs.get("decode", True):
             return Pose2VideoPipelineOutput(videos=latents) if return_dict else latents
+        if output_type == "jpeg":
+            images = self.decode_latents_jpeg(latents, kwargs.get("window_group"), kwargs.get("jpeg_quality", 90),
+                                              kwargs.get("jpeg_subsampling", "4:2:0"))
+            return Pose2VideoPipelineOutput(videos=images) if return_dict else images
         images = self.decode_latents(latents, kwargs.get("window_group"), uint8=output_type == "uint8")
         if output_type in ("tensor", "uint8"):
             images = torch.from_numpy(images)

@@ -383,3 +383,17 @@ class AutoencoderKL:
             y = hip.frames_to_u8(self.decode_nhwc(x), 0.5, 0.5)                    # ((b fc), H, W, 3)
             outs.append(y.view(b, -1, *y.shape[1:]))
         return torch.cat(outs, dim=1)
+
+    def decode_video_jpeg(self, latents, quality=90, subsampling="4:2:0", frames_per_batch=8):
+        """decode_video_uint8's frames as baseline JPEG files (mmgt_amd.video_out.encode_jpeg_frames, csrc/mjpeg.hip), batch by batch without
+        leaving the device: latents (1, 4, f, h, w) -> f byte strings.  What crosses PCIe is the size of the JPEGs, not 3 bytes per pixel."""
+        from .video_out import encode_jpeg_frames
+        lat = latents.to(self._device, torch.float32).contiguous()
+        if lat.shape[0] != 1:
+            raise ValueError(f"decode_video_jpeg: one clip at a time (batch 1), got batch {lat.shape[0]}")
+        out = []
+        for f0 in range(0, lat.shape[2], frames_per_batch):
+            chunk = lat[:, :, f0:f0 + frames_per_batch].contiguous()
+            x = hip.ncfhw_to_nhwc(chunk, 64, self._dtype, scale=1.0 / 0.18215)
+            out += encode_jpeg_frames(hip.frames_to_u8(self.decode_nhwc(x), 0.5, 0.5), quality, subsampling)
+        return out

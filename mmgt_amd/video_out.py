@@ -2,8 +2,10 @@
 (src/utils/util.py:76-107,148-165).  The uint8 conversion runs on the device (AutoencoderKL.decode_video_uint8,
 csrc/conditioning.hip: mmgt_frames_to_u8); this module only lays frames out and writes them.  The reference's .mp4 branch
 encodes with PyAV / libx264, which is not part of this build: .gif goes through PIL exactly as the reference's .gif branch does,
-.npy stores the raw uint8 frames, .mp4 raises."""
+.npy stores the raw uint8 frames, .mp4 raises.  .avi is this build's video file: baseline JPEG frames encoded on the device
+(csrc/mjpeg.hip; encode_jpeg_frames) in a RIFF AVI 1.0 container with an optional PCM sound track (write_avi)."""
 import os
+import struct
 from pathlib import Path
 
 import numpy as np
@@ -33,7 +35,148 @@ def frames_uint8(videos, n_rows=6) -> np.ndarray:
     return grid
 
 
-def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8):
+# ---- JFIF headers: everything of a frame's file that does not depend on its pixels (T.81 Annex B, JFIF 1.01) ----------------------------------
+# T.81 Annex K.3 BITS / HUFFVAL of the four standard Huffman tables (the same tables csrc/mjpeg.hip codes with)
+_DC_BITS = (bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]), bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]))
+_AC_BITS = (bytes([0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125]), bytes([0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119]))
+_AC_VALS = (bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43444546"
+    "4748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7"
+    "b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"), bytes.fromhex(
+    "000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a35363738393a434445"
+    "464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5"
+    "b6b7b8b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"))
+
+
+def _seg(marker, body):
+    return bytes([0xFF, marker]) + struct.pack(">H", len(body) + 2) + body
+
+
+def jfif_headers(width, height, quality=90, subsampling="4:2:0") -> bytes:
+    """SOI .. SOS of a frame: APP0 (JFIF 1.01, 1:1 aspect), two DQT, SOF0 with the TRUE size, the four Annex K DHT, DRI (one MCU row) and the
+    scan header.  What follows in the file is the entropy-coded data with its RSTm markers and EOI, as the device lays it out."""
+    from . import hip
+    ql, qc = hip.jpeg_qtables(quality)
+    _, mcu_cols, bpm = hip.jpeg_geometry(height, width, subsampling)
+    out = b"\xff\xd8" + _seg(0xE0, b"JFIF\0" + bytes([1, 1, 0]) + struct.pack(">HH", 1, 1) + b"\0\0")
+    out += _seg(0xDB, b"\x00" + ql) + _seg(0xDB, b"\x01" + qc)
+    y_hv = 0x22 if bpm == 6 else 0x11
+    out += _seg(0xC0, struct.pack(">BHHB", 8, height, width, 3) + bytes([1, y_hv, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for cls_id, bits, vals in ((0x00, _DC_BITS[0], bytes(range(12))), (0x10, _AC_BITS[0], _AC_VALS[0]),
+                               (0x01, _DC_BITS[1], bytes(range(12))), (0x11, _AC_BITS[1], _AC_VALS[1])):
+        out += _seg(0xC4, bytes([cls_id]) + bits + vals)
+    out += _seg(0xDD, struct.pack(">H", mcu_cols))
+    out += _seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
+    return out
+
+
+JPEG_SCRATCH_BYTES = 256 << 20      # encode_jpeg_frames codes at most this much worst-case segment space per set of launches
+
+
+def encode_jpeg_frames(frames, quality=90, subsampling="4:2:0") -> list:
+    """(n, H, W, 3) uint8 RGB frames (a CUDA tensor, or host data that is uploaded) -> n byte strings, each a complete baseline JFIF file.
+    Colour transform, DCT, quantiser, Huffman coding, byte stuffing and compaction run on the device (csrc/mjpeg.hip); the host receives the
+    offsets and ONE buffer of scan data and prepends the fixed headers.  The bytes are the same on every call."""
+    from . import hip
+    x = torch.as_tensor(frames)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"encode_jpeg_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
+    if not x.is_cuda:
+        x = x.cuda()
+    x = x.contiguous()
+    n, H, W, _ = x.shape
+    if n == 0:
+        return []
+    head = jfif_headers(W, H, quality, subsampling)                          # also the argument check: the library refuses bad ones
+    rows = hip.jpeg_geometry(H, W, subsampling)[0]
+    per_call = max(1, JPEG_SCRATCH_BYTES // (rows * hip.jpeg_segment_stride(W, subsampling)))
+    out = []
+    for f0 in range(0, n, per_call):
+        part = x[f0:f0 + per_call]
+        segs, sizes = hip.jpeg_entropy(hip.jpeg_dct_quant(part, quality, subsampling), H, W, subsampling)
+        data, off = hip.jpeg_compact(segs, sizes, rows)
+        data = data.cpu().numpy().tobytes()
+        off = off.tolist()
+        out += [head + data[off[k * rows]:off[(k + 1) * rows]] for k in range(part.shape[0])]
+    return out
+
+
+# ---- RIFF AVI 1.0 ------------------------------------------------------------------------------------------------------------------------------
+AVI_MAX_BYTES = 1 << 30             # one RIFF chunk; larger files need OpenDML (AVIX), which is not written
+
+
+def _chunk(fourcc: bytes, body: bytes) -> bytes:
+    return fourcc + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")
+
+
+def write_avi(path, jpeg_frames, width, height, fps, audio=None):
+    """Motion-JPEG AVI: RIFF 'AVI ' { LIST 'hdrl' { avih, LIST 'strl' { strh vids/MJPG, strf BITMAPINFOHEADER } [, LIST 'strl' { strh auds,
+    strf WAVEFORMATEX PCM }] }, LIST 'movi' { 00dc [01wb] ... }, idx1 }.  `jpeg_frames`: one complete JPEG file per frame;
+    `audio` = (int16 samples (n, channels) or (n,), sample rate): interleaved as one 01wb chunk of a video frame's duration after each 00dc
+    chunk (any remainder after the last frame).  Chunks are padded to even length; idx1 offsets count from the 'movi' fourcc.  DESIGN.md lists
+    the fields."""
+    frames = [bytes(f) for f in jpeg_frames]
+    if not frames:
+        raise ValueError("write_avi: no frames")
+    fps = float(fps)
+    usec = int(round(1e6 / fps))
+    rate, scale = (int(fps), 1) if fps == int(fps) else (int(round(fps * 1000)), 1000)
+    pcm, channels, srate, block = None, 0, 0, 0
+    if audio is not None:
+        samples, srate = audio
+        samples = np.ascontiguousarray(np.asarray(samples))
+        if samples.dtype != np.int16 or samples.ndim not in (1, 2):
+            raise ValueError(f"write_avi: audio must be int16 samples (n, channels), got {samples.dtype} {samples.shape}")
+        samples = samples.reshape(samples.shape[0], -1)
+        channels, srate = samples.shape[1], int(srate)
+        block = 2 * channels
+        pcm = samples.astype("<i2").tobytes()
+    est = sum(len(f) + 50 for f in frames) + (len(pcm) if pcm else 0) + 4096      # chunk headers, padding, index entries: an upper estimate
+    if est > AVI_MAX_BYTES:
+        raise ValueError(f"write_avi: {path} would pass 1 GiB (about {est} bytes); AVI 1.0 holds one RIFF chunk and OpenDML is not written")
+
+    movi, index = [b"movi"], []
+    pos = 4                                                                  # offset of the next chunk from the 'movi' fourcc
+
+    def add(fourcc, body, flags):
+        nonlocal pos
+        index.append(fourcc + struct.pack("<III", flags, pos, len(body)))
+        c = _chunk(fourcc, body)
+        movi.append(c)
+        pos += len(c)
+
+    n = len(frames)
+    total_samples = len(pcm) // block if pcm else 0
+    for k, f in enumerate(frames):
+        add(b"00dc", f, 0x10)                                                # AVIIF_KEYFRAME: every JPEG frame is one
+        if pcm:
+            a = min(total_samples, int(round(k * srate / fps)))
+            b = total_samples if k == n - 1 else min(total_samples, int(round((k + 1) * srate / fps)))
+            if b > a:
+                add(b"01wb", pcm[a * block:b * block], 0x10)
+    movi = b"".join(movi)
+    streams = 2 if pcm else 1
+    big = max(len(f) for f in frames)
+    avih = struct.pack("<14I", usec, int(big * fps) + (srate * block), 0, 0x10 | (0x100 if pcm else 0),       # AVIF_HASINDEX | AVIF_ISINTERLEAVED
+                       n, 0, streams, big, width, height, 0, 0, 0, 0)
+    strh_v = b"vids" + b"MJPG" + struct.pack("<IHHIIIIIIII4H", 0, 0, 0, 0, scale, rate, 0, n, big, 0xFFFFFFFF, 0, 0, 0, width, height)
+    strf_v = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+    hdrl = b"hdrl" + _chunk(b"avih", avih) + _chunk(b"LIST", b"strl" + _chunk(b"strh", strh_v) + _chunk(b"strf", strf_v))
+    if pcm:
+        strh_a = b"auds" + b"\0\0\0\0" + struct.pack("<IHHIIIIIIII4H", 0, 0, 0, 0, block, srate * block, 0, total_samples, srate * block // 2,
+                                                      0xFFFFFFFF, block, 0, 0, 0, 0)
+        strf_a = struct.pack("<HHIIHHH", 1, channels, srate, srate * block, block, 16, 0)                     # WAVE_FORMAT_PCM
+        hdrl += _chunk(b"LIST", b"strl" + _chunk(b"strh", strh_a) + _chunk(b"strf", strf_a))
+    body = b"AVI " + _chunk(b"LIST", hdrl) + _chunk(b"LIST", movi) + _chunk(b"idx1", b"".join(index))
+    if len(body) + 8 > AVI_MAX_BYTES:
+        raise ValueError(f"write_avi: {path} would pass 1 GiB ({len(body) + 8} bytes); AVI 1.0 holds one RIFF chunk and OpenDML is not written")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+    return len(body) + 8
+
+
+def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90):
     if rescale:
         if torch.as_tensor(videos).dtype == torch.uint8:
             raise ValueError("rescale=True maps [-1, 1] floats to [0, 1]; uint8 frames are already in their final range")
@@ -50,6 +193,8 @@ def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8):
         pil[0].save(fp=path, format="GIF", append_images=pil[1:], save_all=True, duration=(1 / fps * 1000), loop=0)
     elif fmt == ".npy":
         np.save(path, frames)
+    elif fmt == ".avi":
+        write_avi(path, encode_jpeg_frames(frames, quality), frames.shape[2], frames.shape[1], fps)
     elif fmt == ".mp4":
         raise RuntimeError("mp4 output needs PyAV / libx264 (src/utils/util.py:83-97), which this build does not include: "
                            "write .gif or .npy, or hand frames_uint8() to your encoder")

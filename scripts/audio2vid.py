@@ -56,7 +56,9 @@ def parse_args():
     p.add_argument("--motion_diffusion_ckpt", type=str, default="./pretrained_weights/MMGT_pretrained/stage_1/audio2pose_best_model.pt")
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--format", default="npy", choices=["npy", "gif"])
+    p.add_argument("--format", default="npy", choices=["npy", "gif", "avi"],
+                   help="avi = Motion-JPEG encoded on the device, with the samples of --audio_path as its PCM sound track")
+    p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
     p.add_argument("--wavlm", default="off", metavar="{off,random,PATH}",
                    help="WavLM-Large features of --audio_path as columns 0:1024 of the SMGA conditioning: off (hash-seeded stand-in, the default), "
                         "random (hash-seeded Large weights) or the path of a WavLM-Large.pt checkpoint")
@@ -110,6 +112,16 @@ def read_wav_16k(path):
             raise SystemExit(f"audio2vid: {path} must be 16-bit PCM")
         pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, w.getnchannels())
     return torch.from_numpy(pcm.astype(np.float32).mean(1) / 32768.0)
+
+
+def read_wav_pcm(path, seconds):
+    """The first `seconds` of a 16-bit PCM .wav as it is stored: (int16 samples (n, channels), sample rate) for write_avi's sound track."""
+    import wave
+    with wave.open(path, "rb") as w:
+        if w.getsampwidth() != 2:
+            raise SystemExit(f"audio2vid: {path} must be 16-bit PCM")
+        n = min(w.getnframes(), int(round(seconds * w.getframerate())))
+        return np.frombuffer(w.readframes(n), dtype="<i2").reshape(-1, w.getnchannels()), w.getframerate()
 
 
 def main():
@@ -227,7 +239,16 @@ def main():
     timing["stage2_s"] = round(time.time() - t0, 3)
     v = torch.as_tensor(out.videos)                                                                          # (1, L, H, W, 3) uint8
     path = os.path.join(a.out_dir, f"audio2vid_synth_{a.W}x{a.H}x{a.L}.{a.format}")
-    save_videos_grid(v, path, n_rows=1, fps=a.fps or 25)
+    if a.format == "avi":                                  # JPEG on the device, the wav's own samples (the first L / fps seconds) as the sound track
+        from mmgt_amd.video_out import encode_jpeg_frames, write_avi
+        fps = a.fps or 25
+        t0 = time.time()
+        jpegs = encode_jpeg_frames(v[0], a.quality)
+        sound = read_wav_pcm(a.audio_path, a.L / fps) if a.audio_path else None
+        extra["bytes"] = write_avi(path, jpegs, a.W, a.H, fps, audio=sound)
+        extra["encode_s"] = round(time.time() - t0, 3)
+    else:
+        save_videos_grid(v, path, n_rows=1, fps=a.fps or 25)
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
                       "dtype": a.dtype, "keypoints_finite": bool(np.isfinite(kps).all()),
                       "mask_levels": [list(m.shape) for m in face], **timing, **extra}))

@@ -48,7 +48,9 @@ def parse_args():
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--random-weights", action="store_true",
                    help="file inputs with the hash-seeded random initialisation instead of the checkpoints of --config")
-    p.add_argument("--format", default="gif", choices=["gif", "npy"], help="output container of the file-input mode")
+    p.add_argument("--format", default="gif", choices=["gif", "npy", "avi"],
+                   help="output container of the file-input mode; avi = Motion-JPEG encoded on the device (mmgt_amd.video_out)")
+    p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -160,15 +162,21 @@ def run_files(a, dev, dtype):
     torch.cuda.synchronize()
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, L, a.steps, a.cfg, generator=gen, motion_scale=[1.0, 1.0, 2.0],
-               context_frames=a.num_c, output_type="uint8")
+               context_frames=a.num_c, output_type="jpeg" if a.format == "avi" else "uint8", jpeg_quality=a.quality)
     torch.cuda.synchronize()
     dt = time.time() - t0
     save_dir = os.path.join(a.out_dir, f"multi_person_{a.num_c}")
     path = os.path.join(save_dir, f"{os.path.splitext(os.path.basename(a.image_path))[0]}.{a.format}")
-    save_videos_grid(out.videos, path, n_rows=1, fps=a.fps)
-    v = torch.as_tensor(out.videos)
-    print(json.dumps({"video": list(v.shape), "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
-                      "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype}))
+    extra = {}
+    if a.format == "avi":                                     # the frames left the device as JPEG files: only the container is written here
+        from mmgt_amd.video_out import write_avi
+        extra = {"bytes": write_avi(path, out.videos, a.W, a.H, a.fps), "quality": a.quality}
+        shape = [1, len(out.videos), a.H, a.W, 3]
+    else:
+        save_videos_grid(out.videos, path, n_rows=1, fps=a.fps)
+        shape = list(torch.as_tensor(out.videos).shape)
+    print(json.dumps({"video": shape, "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
+                      "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype, **extra}))
 
 
 def main():
