@@ -290,6 +290,12 @@ int mmgt_accumulate_window(const void* pred, float* pred_sum, float* counter, co
 int mmgt_accumulate_window_rows(const void* pred, float* pred_sum, float* counter, const int* idx, int Fw, int F, int C,
                                 int Cpad, int hw, int rows, int row0, int bump_counter, int dtype, void* stream);
 
+/* The B windows of one sampler group (context_batch_size = B) in one launch: pred is ((2*B*Fw), hw, Cpad) in CFG row major order
+ * [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)], idx int32 [B][Fw].  The windows are added in list order (they may share frames) and
+ * counter is bumped once per window: bitwise what B calls of mmgt_accumulate_window on the windows' own slices give.  No atomics. */
+int mmgt_accumulate_windows(const void* pred, float* pred_sum, float* counter, const int* idx, int B, int Fw, int F, int C, int Cpad,
+                            int hw, int dtype, void* stream);
+
 /* ---- Stage-1 SMGA audio -> pose sampler: the element-wise glue between its Linear / attention / LayerNorm calls.
  * out = x rotated pairwise by the angle table cos_sin[(row % seq)][dim / 2][2] (cos, sin): RotaryEmbedding.rotate_queries_or_keys,
  * src/audio2pose_model/rotary_embedding_torch.py:38-61,106-113 (call sites model.py:121,267,298-299). */

@@ -122,6 +122,49 @@ __global__ void accumulate_window_kernel(const T* __restrict__ pred, float* __re
   if (bump && blockIdx.x == 0 && threadIdx.x < Fw) counter[idx[threadIdx.x]] += 1.f;
 }
 
+// The B windows of one sampler group in ONE launch (context_batch_size = B): pred ((2 B Fw), hw, Cpad) in CFG row major order [uncond w0 ..
+// uncond w(B-1), cond w0 .. cond w(B-1)], idx [B][Fw].  Windows of a group may share frames, and the order of the fp32 adds is part of the
+// sampler's definition, so a thread owns one TARGET element (row, c, frame, pixel) and adds the windows that hold its frame in list order:
+// no atomics, bitwise what B launches of accumulate_window_kernel give.  blockIdx.y = target frame; match[k] = position of that frame in
+// window k (indices are distinct inside a window) or -1.
+template <typename T>
+__global__ __launch_bounds__(256) void accumulate_windows_kernel(const T* __restrict__ pred, float* __restrict__ ps, float* __restrict__ counter,
+                                                                 const int* __restrict__ idx, int B, int Fw, int F, int C, int Cpad, int hw) {
+  __shared__ int match[256];
+  const int f = blockIdx.y;
+  for (int k = threadIdx.x; k < B; k += blockDim.x) {
+    int j = -1;
+    for (int i = 0; i < Fw; ++i)
+      if (idx[k * Fw + i] == f) j = i;
+    match[k] = j;
+  }
+  __syncthreads();
+  const long total = 2L * C * hw;
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i < total) {
+    const int p = i % hw;
+    const long t = i / hw;
+    const int c = t % C;
+    const int r = t / C;
+    float* dst = ps + (((long)r * C + c) * F + f) * hw + p;
+    float acc = *dst;
+    bool any = false;
+    for (int k = 0; k < B; ++k) {
+      const int j = match[k];
+      if (j < 0) continue;
+      acc += Elem<T>::ld(pred + ((((long)r * B + k) * Fw + j) * hw + p) * Cpad + c);
+      any = true;
+    }
+    if (any) *dst = acc;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    float cnt = counter[f];
+    for (int k = 0; k < B; ++k)
+      if (match[k] >= 0) cnt += 1.f;
+    counter[f] = cnt;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const T* __restrict__ x, long ldx, T* __restrict__ out,
                                                            long ldo, int rows, int cols, float scale) {
@@ -340,6 +383,24 @@ extern "C" int mmgt_accumulate_window_rows(const void* pred, float* pred_sum, fl
 extern "C" int mmgt_accumulate_window(const void* pred, float* pred_sum, float* counter, const int* idx, int Fw, int F,
                                       int C, int Cpad, int hw, int dtype, void* stream) {
   return mmgt_accumulate_window_rows(pred, pred_sum, counter, idx, Fw, F, C, Cpad, hw, 2, 0, 1, dtype, stream);
+}
+
+extern "C" int mmgt_accumulate_windows(const void* pred, float* pred_sum, float* counter, const int* idx, int B, int Fw, int F, int C,
+                                       int Cpad, int hw, int dtype, void* stream) {
+  MMGT_CHECK(pred && pred_sum && counter && idx, "accumulate_windows: null pointer");
+  MMGT_CHECK(B > 0 && B <= 256, "accumulate_windows: %d windows in a group (1 .. 256)", B);
+  MMGT_CHECK(Fw > 0 && F >= Fw && F <= 65535 && C > 0 && Cpad >= C && hw > 0, "accumulate_windows: bad sizes");
+  MMGT_CHECK(dtype == MMGT_F32 || dtype == MMGT_BF16, "accumulate_windows: bad dtype");
+  const long total = 2L * C * hw;
+  const dim3 grid((unsigned)((total + 255) / 256), (unsigned)F);
+  if (dtype == MMGT_BF16)
+    hipLaunchKernelGGL(accumulate_windows_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, pred_sum, counter, idx,
+                       B, Fw, F, C, Cpad, hw);
+  else
+    hipLaunchKernelGGL(accumulate_windows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pred, pred_sum, counter, idx,
+                       B, Fw, F, C, Cpad, hw);
+  MMGT_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int mmgt_softmax_rows(const void* x, long ldx, void* out, long ldo, int rows, int cols, float scale, int dtype,

@@ -114,6 +114,7 @@ _SIGS = {
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_accumulate_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -847,6 +848,21 @@ def accumulate_window(pred, pred_sum, counter, idx, C, rows=2, row0=0, bump_coun
     _check(lib().mmgt_accumulate_window_rows(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), Fw, F, C, pred.shape[3],
                                              hw, rows, row0, int(bump_counter), dtype_code(pred.dtype), _stream()),
            "mmgt_accumulate_window_rows")
+
+
+def accumulate_windows(pred, pred_sum, counter, idx, C):
+    """The B windows of one sampler group in one launch: pred ((2*B*Fw), H, W, cpad) channels-last in CFG row major order [uncond w0 ..
+    uncond w(B-1), cond w0 .. cond w(B-1)], idx (B, Fw) int32 on the device.  Added window by window in list order, counter bumped once per
+    window: bitwise what B calls of `accumulate_window` on the windows' slices give."""
+    _dev(pred, pred_sum, counter, idx)
+    assert idx.dtype == torch.int32 and idx.dim() == 2 and idx.is_contiguous() and pred.is_contiguous() and pred_sum.is_contiguous()
+    B, Fw = idx.shape
+    F = pred_sum.shape[2]
+    hw = pred.shape[1] * pred.shape[2]
+    assert pred.shape[0] == 2 * B * Fw and pred_sum.shape[0] == 2 and pred_sum.shape[1] == C and pred_sum.shape[3] * pred_sum.shape[4] == hw
+    assert counter.numel() == F and counter.dtype == torch.float32 and pred_sum.dtype == torch.float32
+    _check(lib().mmgt_accumulate_windows(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), B, Fw, F, C, pred.shape[3], hw,
+                                         dtype_code(pred.dtype), _stream()), "mmgt_accumulate_windows")
 
 
 # ------------------------------------------------------------------------------------------------------------ SMGA glue

@@ -8,6 +8,7 @@ in two HIP kernels on fp32 latents that never leave the GPU.
 Extensions through **kwargs (allowed by the reference signature, :365): `latents=` (inject initial noise, parity tests),
 `clip_image_embeds=` / `ref_image_latents=` / `reference_banks=` / `pose_features=` (hand over prologue results when the module
 is None), `decode=False`, `window_group=` / `cfg_split=` (window-parallel sampling of one long video over several GPUs).
+`context_batch_size=B` runs the window loop B windows per forward: the same sampler as B = 1 (see `denoise`).
 `output_type="uint8"` returns the frames as uint8 (b, f, H, W, 3), converted on the device (what save_videos_grid writes).
 `output_type="jpeg"` (with `jpeg_quality=`, `jpeg_subsampling=`) returns one JPEG file (bytes) per frame, encoded on the device.
 """
@@ -125,10 +126,14 @@ class Pose2VideoPipeline:
     def _pose_window(self, pose_fea, c):
         """Pose features of one window for both CFG rows (pipeline_pose2vid_long.py:576-580), converted ONCE to the
         operator's channels-last layout and dtype: they are step-invariant, so the per-step forward takes them as is."""
+        return self._pose_group(pose_fea, [c])
+
+    def _pose_group(self, pose_fea, cs):
+        """The same for the windows `cs` of one group, CFG row major: [w0 .. w(B-1), w0 .. w(B-1)]."""
         if pose_fea is None:
             return None
         unet = self.denoising_unet
-        p5 = pose_fea[:, :, c].repeat(2, 1, 1, 1, 1).to(torch.float32).contiguous()
+        p5 = torch.cat([pose_fea[:, :, c] for c in cs]).repeat(2, 1, 1, 1, 1).to(torch.float32).contiguous()
         if not p5.is_cuda or not hasattr(unet, "boc"):
             return p5
         return hip.ncfhw_to_nhwc(p5, p5.shape[1], unet.dtype)
@@ -137,7 +142,7 @@ class Pose2VideoPipeline:
     def denoise(self, latents, timesteps, encoder_hidden_states, pose_fea, audio_tensor_pre, full_masks, face_masks,
                 lip_masks, guidance_scale, motion_scale, context_frames, context_stride, context_overlap,
                 context_schedule="uniform", num_inference_steps=None, callback=None, callback_steps=1,
-                window_group=None, cfg_split="auto"):
+                window_group=None, cfg_split="auto", context_batch_size=1):
         """pipeline_pose2vid_long.py:494-643.  latents (1, C, L, h, w) fp32 on the GPU; returns the final latents.
 
         window_group: a torch.distributed process group (or True for the default group) turns on window-parallel sampling of
@@ -146,7 +151,22 @@ class Pose2VideoPipeline:
         to the C valid channels (fp32 (rows * Fw, h, w, C): 1.57 MB per CFG row at 24 x 64 x 64 x 4), and every rank then
         accumulates ALL units in the reference's window order and applies the identical overlap-average + CFG + DDIM update --
         so the latents stay bit-identical on every rank, with no other exchange.  cfg_split: "auto" splits the CFG rows when
-        that shortens the critical path (6 windows on 4 ranks: 3 rounds of half units instead of 2 rounds of whole ones)."""
+        that shortens the critical path (6 windows on 4 ranks: 3 rounds of half units instead of 2 rounds of whole ones).
+
+        context_batch_size = B > 1 is the SAME sampler as B = 1 with B windows per forward: the scheduler's window list is taken in its
+        order in groups of B (the last group may be smaller), one group is one call of the operator with the rows in CFG row major order
+        [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)], and the predictions are added to pred_sum / counter window by window in list
+        order (hip.accumulate_windows), so the fp32 accumulation order of the overlap average is that of B = 1.  Only the rounding inside the
+        UNet may differ (dispatch picks tiles by the row count).  The reference's own handling of the argument is inconsistent (App. C-7)
+        and is not reproduced.  Not combined with window_group: raises ValueError."""
+        B = int(context_batch_size)
+        if B < 1:
+            raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
+        if B > 1 and window_group is not None:
+            raise ValueError("context_batch_size > 1 is not combined with window_group (window-parallel sampling deals single windows or "
+                             "single CFG rows to the ranks): use one of the two")
+        if B > 1 and latents.shape[0] != 1:
+            raise ValueError("context_batch_size > 1 batches windows of ONE clip: latents must be (1, C, L, h, w)")
         video_length = latents.shape[2]
         dev = latents.device
         sched = get_context_scheduler(context_schedule)
@@ -155,15 +175,29 @@ class Pose2VideoPipeline:
         windows = list(sched(0, nsteps, video_length, context_frames, context_stride, context_overlap))
         win_idx = [torch.tensor(c, device=dev, dtype=torch.int32) for c in windows]
         win_long = [torch.tensor(c, device=dev, dtype=torch.long) for c in windows]
-        # per-window conditioning is step-invariant: gather it once
-        cond = []
-        for c in win_long:
-            cond.append(dict(
-                pose=self._pose_window(pose_fea, c),
-                audio=audio_tensor_pre[:, c].contiguous(),
-                full=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in full_masks],
-                face=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in face_masks],
-                lips=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in lip_masks]))
+        # per-window conditioning is step-invariant: gather it once -- per window (B = 1, and the units of window_group), or per group of B windows
+        # in list order, cut in CFG row major order
+        cond, groups = [], []
+        if B == 1:
+            for c in win_long:
+                cond.append(dict(
+                    pose=self._pose_window(pose_fea, c),
+                    audio=audio_tensor_pre[:, c].contiguous(),
+                    full=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in full_masks],
+                    face=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in face_masks],
+                    lips=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in lip_masks]))
+        else:
+            for g0 in range(0, len(windows), B):
+                ws = list(range(g0, min(g0 + B, len(windows))))
+                if len({len(windows[w]) for w in ws}) != 1:
+                    raise RuntimeError("context_batch_size > 1: the windows of a group must have the same length")
+                gl = torch.stack([win_long[w] for w in ws])                                   # (Bg, Fw)
+                rows = lambda t: t.view(2, video_length, -1)[:, gl].reshape(-1, t.shape[-1]).contiguous()     # (2, Bg, Fw, n) -> (2 Bg Fw, n)
+                groups.append(dict(
+                    n=len(ws), idx=torch.stack([win_idx[w] for w in ws]).contiguous(), long=gl,
+                    pose=self._pose_group(pose_fea, [win_long[w] for w in ws]),
+                    audio=audio_tensor_pre[:, gl].reshape(2 * len(ws), gl.shape[1], *audio_tensor_pre.shape[2:]).contiguous(),
+                    full=[rows(t) for t in full_masks], face=[rows(t) for t in face_masks], lips=[rows(t) for t in lip_masks]))
         # the reference's unconditional audio row is zeros_like(audio) (:484-485): checked once here (one device sync per clip), and the
         # operator then skips that row's audio cross-attention, whose result is exactly zero
         hip_op = hasattr(self.denoising_unet, "boc")                # the HIP operator (CPU doubles of the tests take no extras)
@@ -196,6 +230,21 @@ class Pose2VideoPipeline:
                                            lips=[cut(t) for t in cd["lips"]])
             return half_cond[(w, row)]
 
+        def run_group(gd, t):
+            """One forward for the windows of a group: (2 Bg, C, Fw, h, w) in, ((2 Bg Fw), h, w, 64) channels-last out.  (The keyword
+            assembly repeats run_unit's on purpose: the B = 1 path stays as it was; fold the two when a default other than 1 is chosen.)"""
+            lat_g = self.scheduler.scale_model_input(latents[0][:, gd["long"]].permute(1, 0, 2, 3, 4), t).repeat(2, 1, 1, 1, 1)
+            kw = {}
+            if keep_window_state:                                # one memo per GROUP: its audio K / V and mask rows belong to these windows alone
+                kw["window_state"] = gd.setdefault("state", {})
+            if uncond_audio_zero:
+                kw["audio_zero_rows"] = gd["n"]
+            if hip_op:
+                kw["cfg_rows_share_input"] = True                # .repeat(2 ...) above and in _pose_group: the second half is a copy of the first
+            return self.denoising_unet.denoise_window(
+                lat_g, t, encoder_hidden_states=encoder_hidden_states, audio_embedding=gd["audio"], pose_cond_fea=gd["pose"],
+                full_mask=gd["full"], face_mask=gd["face"], body_mask=gd["lips"], motion_scale=motion_scale, **kw)
+
         for i, t in enumerate(timesteps):
             pred_sum = torch.zeros((2,) + tuple(latents.shape[1:]), device=dev, dtype=torch.float32)
             counter = torch.zeros((video_length,), device=dev, dtype=torch.float32)
@@ -218,7 +267,10 @@ class Pose2VideoPipeline:
                     pose_cond_fea=cd["pose"], full_mask=cd["full"], face_mask=cd["face"], body_mask=cd["lips"],
                     motion_scale=motion_scale, **kw)
 
-            if window_group is None:
+            if B > 1:
+                for gd in groups:
+                    hip.accumulate_windows(run_group(gd, t), pred_sum, counter, gd["idx"], C)
+            elif window_group is None:
                 for w in range(len(windows)):
                     hip.accumulate_window(run_unit(w, None), pred_sum, counter, win_idx[w], C)
             else:
@@ -256,8 +308,8 @@ class Pose2VideoPipeline:
                  **kwargs):
         if eta != 0.0:
             raise NotImplementedError("eta != 0 is not used by the reference scripts")
-        if context_batch_size != 1:
-            raise NotImplementedError("the reference's window loop is only consistent for context_batch_size=1 (App. C-7)")
+        if int(context_batch_size) < 1:
+            raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
         if not guidance_scale > 1.0:
             raise NotImplementedError("classifier-free guidance is mandatory in the reference loop (App. C-7)")
         unet = self.denoising_unet
@@ -314,7 +366,8 @@ class Pose2VideoPipeline:
         latents = self.denoise(latents, timesteps, encoder_hidden_states, pose_fea, audio_pre, full_masks, face_masks,
                                lip_masks, guidance_scale, motion_scale, context_frames, context_stride, context_overlap,
                                context_schedule, num_inference_steps, callback, callback_steps,
-                               window_group=kwargs.get("window_group"), cfg_split=kwargs.get("cfg_split", "auto"))
+                               window_group=kwargs.get("window_group"), cfg_split=kwargs.get("cfg_split", "auto"),
+                               context_batch_size=context_batch_size)
         unet.clear_banks()                                                                # :645-646
 
         if interpolation_factor > 0:

@@ -83,6 +83,19 @@ def mask_bias_columns(rs, ncols, dtype):
     return cols
 
 
+def check_group_operands(b, f, hh, ww, c0, dtype, cfg_row=None):
+    """Refuse a forward that holds SEVERAL windows (b > 2, or b > 1 with cfg_row) when its widest level-0 operand would pass the 2 GiB that the
+    kernels' 32-bit LDS-DMA offsets address (hip.DMA_LIMIT: csrc/gemm16.hip, gemm.hip, attn64.hip / attn80.hip / attention.hip operands).  The
+    widest operands of b * f images of hh x ww tokens: in bf16 the merged MM-HAA operand of `_audio_transformer` (round_up(3 C + 9, 64) = 1024
+    columns at C = 320), in fp32 mode the GEGLU output of the unfused FeedForward (4 C columns).  A lone window is never refused here:
+    `hip.gemm` / `hip.conv3x3` work its oversized operands in runs of rows, as before."""
+    cols, size = (4 * c0, 4) if dtype == torch.float32 else (round_up(3 * c0 + 9, 64), 2)
+    widest = b * f * hh * ww * cols * size
+    if widest > hip.DMA_LIMIT and b > (1 if cfg_row is not None else 2):
+        raise RuntimeError(f"denoise_window: {b} x {f} frames of {hh} x {ww} latents need a {widest / 2 ** 30:.2f} GiB operand; the kernels address "
+                           "2 GiB per tensor (fewer windows per forward: context_batch_size)")
+
+
 class UNet3DConditionModel:
     _supports_gradient_checkpointing = True
 
@@ -614,7 +627,8 @@ class UNet3DConditionModel:
     def _self_attention(self, t, n1, nb, n, inner, bank=None, frames=1, cfg_row=None, norm=None):
         """attn1: q,k from one GEMM, V^T from a batched W.X^T GEMM, flash attention, returns (nb*n, inner).
         cfg_row: None = both CFG rows batched (the bank is read by the second half of the batch only); 0 / 1 = the batch
-        holds the unconditional / conditional row alone (window-parallel sampling splits them over ranks).
+        holds the unconditional / conditional row alone (window-parallel sampling splits them over ranks).  Either form may hold
+        several windows of `frames` images per CFG row (context_batch_size > 1): CFG row major, so "second half" stays true.
         norm: `n1` is the UN-normalised hidden state and `norm` the key of the LayerNorm in front of the attention: LayerNorm, q | k
         and V^T come out of one launch (the 320-channel level, csrc/rowgemm.hip)."""
         hd = inner // self.heads
@@ -632,8 +646,10 @@ class UNet3DConditionModel:
             kb, vbt, nkb = bank
             if cfg_row == 1:                 # only bank row 1 (the conditional row's features) is ever read: SURVEY App. C-6
                 kb, vbt = kb[1:], vbt[1:]
+            # image b reads bank row b // k2_bdiv: with the CFG rows batched the second half of the images (the conditional row of EVERY window
+            # in the batch) maps to row 1, with the conditional row alone every image maps to row 0 of the slice
             kw = dict(k2=kb, v2=vbt, k2_str=(kb.stride(0), kb.stride(1)), v2_str=(vbt.stride(0), vbt.stride(1)),
-                      k2_bdiv=frames, nk2=nkb, seg2_first_batch=0 if cfg_row == 1 else nb // 2)
+                      k2_bdiv=nb if cfg_row == 1 else nb // 2, nk2=nkb, seg2_first_batch=0 if cfg_row == 1 else nb // 2)
         hip.attention(qk, qk[:, inner:], vt, o, batch=nb, heads=self.heads, hd=hd, nq=n, nk=n, scale=hd ** -0.5,
                       q_str=(n * 2 * inner, 0, 2 * inner), k_str=(n * 2 * inner, 0, 2 * inner),
                       v_str=(inner * npad, 0, npad), o_str=(n * inner, 0, inner), v_transposed=True, **kw)
@@ -673,7 +689,8 @@ class UNet3DConditionModel:
         ((2 f), h, w, c) with identical halves.  GroupNorm, proj_in, LayerNorm and q | k | V^T are computed for the f frames once; ONE
         attention pass over the frames' own keys serves both rows -- the unconditional row's output [x] is the state of the conditional
         row's [x | bank] pass after its last own-key tile (mmgt_attention_twin) -- and the rows part at the out-projection, which adds the
-        per-row CLIP constant.  Returns None when the shape has no twin kernel (the caller then runs the batched block)."""
+        per-row CLIP constant.  f = nb / 2 images per half: one window's frames, or the frames of all windows of a group (context_batch_size > 1).
+        Returns None when the shape has no twin kernel (the caller then runs the batched block)."""
         nb, h, ww, c = x2.shape
         f, n = nb // 2, h * ww
         t = p + ".transformer_blocks.0"
@@ -694,7 +711,7 @@ class UNet3DConditionModel:
         hip.attention(qk, qk[:, inner:], vt, o[f * n:], batch=f, heads=self.heads, hd=hd, nq=n, nk=n, scale=hd ** -0.5,
                       q_str=(n * 2 * inner, 0, 2 * inner), k_str=(n * 2 * inner, 0, 2 * inner), v_str=(inner * npad, 0, npad),
                       o_str=(n * inner, 0, inner), v_transposed=True, k2=kb, v2=vbt, k2_str=(kb.stride(0), kb.stride(1)),
-                      v2_str=(vbt.stride(0), vbt.stride(1)), k2_bdiv=frames, nk2=nkb, seg2_first_batch=0, twin_out=o[:f * n])
+                      v2_str=(vbt.stride(0), vbt.stride(1)), k2_bdiv=f, nk2=nkb, seg2_first_batch=0, twin_out=o[:f * n])
         cvec = self._clip_vector(t, ehs)                                                 # (2, inner) fp32: row 0 unconditional
         hid2 = torch.empty((nb * n, inner), device=self._device, dtype=self._dtype)
         for row in (0, 1):
@@ -903,7 +920,7 @@ class UNet3DConditionModel:
                        audio_zero_rows=0, cfg_rows_share_input=False):
         """The operator body; returns the prediction channels-last ((b f), h, w, 64) with the first 4 channels valid
         (what mmgt_accumulate_window consumes, so the sampler never converts layouts).
-        window_state: a dict the CALLER owns, one per (window, CFG row) whose audio / masks / motion_scale do not change between
+        window_state: a dict the CALLER owns, one per (window or group of windows, CFG row) whose audio / masks / motion_scale do not change between
         DDIM steps (the sampler's windows never move, pipeline_pose2vid_long.py:534-543): the operator keeps what it derives from those
         inputs alone in it -- the audio K / V projections of the six audio modules, the mask rows of MM-HAA -- instead of recomputing
         them at every step.  None: nothing is kept.
@@ -911,11 +928,18 @@ class UNet3DConditionModel:
         the sampler builds them; conv_in and the first resnet then run once.
         audio_zero_rows: the CALLER's statement that the audio embedding of the first `audio_zero_rows` batch rows is all zero (the
         unconditional CFG row, pipeline_pose2vid_long.py:484-485); their audio cross-attention is exactly 0 and is not computed.
-        cfg_row (0 or 1): `sample`, the audio, pose and masks hold ONE CFG row (b = 1) -- the unconditional row never reads
+        cfg_row (0 or 1): `sample`, the audio, pose and masks hold ONE CFG row -- the unconditional row never reads
         the reference banks, the conditional row reads them in every frame; `encoder_hidden_states` stays the (2, 1, 768)
-        pair.  The window-parallel sampler deals the two rows of a window to different GPUs."""
-        if cfg_row is not None and (cfg_row not in (0, 1) or sample.shape[0] != 1 or encoder_hidden_states.shape[0] != 2):
-            raise RuntimeError("cfg_row: one CFG row (b = 1) with the (2, ...) encoder_hidden_states pair")
+        pair.  The window-parallel sampler deals the two rows of a window to different GPUs.
+        Several windows of ONE clip in one forward (the sampler's context_batch_size = B): `sample` is (2 B, 4, Fw, h, w) in CFG row major
+        order [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)] (or (B, ...) with cfg_row); audio, pose and masks follow the same order.
+        The windows share the banks, the (2, 1, 768) pair and the timestep; the temporal sequences stay Fw frames long.  audio_zero_rows is
+        then B, and cfg_rows_share_input says that the second HALF of the batch is a copy of the first.  window_state: one dict per group."""
+        if cfg_row is not None and (cfg_row not in (0, 1) or encoder_hidden_states.shape[0] != 2):
+            raise RuntimeError("cfg_row: one CFG row (0 or 1) with the (2, ...) encoder_hidden_states pair")
+        if cfg_row is None and (sample.shape[0] % 2 or encoder_hidden_states.shape[0] != 2):
+            raise RuntimeError(f"denoise_window: {sample.shape[0]} batch rows with {encoder_hidden_states.shape[0]} encoder_hidden_states rows: the "
+                               "batch is the CFG pair of one or more windows, [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)], or one row with cfg_row")
         if not self._loaded:
             raise RuntimeError("UNet3DConditionModel.forward before load_state_dict")
         if not sample.is_cuda:
@@ -923,6 +947,7 @@ class UNet3DConditionModel:
         b, cin, f, hh, ww = sample.shape
         if hh % 8 or ww % 8:
             raise RuntimeError("latent height/width must be multiples of 8 (unet_3d.py:461-469)")
+        check_group_operands(b, f, hh, ww, self.boc[0], self._dtype, cfg_row)
         lpb = self.config.layers_per_block
         # scripts leave the module in train() + gradient checkpointing => motion_scale applied
         ms = motion_scale if (self.training and self.gradient_checkpointing) else None
@@ -940,11 +965,12 @@ class UNet3DConditionModel:
         # The two CFG rows of a pair enter with the SAME latents, pose features and timestep (the caller says so: cfg_rows_share_input);
         # they stay identical until the first transformer reads the per-row conditioning, so conv_in and the first ResnetBlock3D are
         # computed once for the f frames and duplicated (pipeline_pose2vid_long.py:554-580: `latent_model_input = latents.repeat(2 ...)`).
-        shared = bool(cfg_rows_share_input) and b == 2 and cfg_row is None and self._share_rows
+        shared = bool(cfg_rows_share_input) and b >= 2 and cfg_row is None and self._share_rows
+        hf = b // 2 * f                                 # images of one CFG row: the frames of every window in the batch
         if shared:
-            x2 = torch.empty((2 * f, hh, ww, self.boc[0]), device=self._device, dtype=self._dtype)
-            x = hip.conv3x3(x[:f], self.w["conv_in.w"], self.w["conv_in.bias"], residual=None if pose is None else pose[:f], out=x2[:f])
-            x2[f:].copy_(x)                             # (one half-tensor copy; torch.cat would read and write both halves)
+            x2 = torch.empty((2 * hf, hh, ww, self.boc[0]), device=self._device, dtype=self._dtype)
+            x = hip.conv3x3(x[:hf], self.w["conv_in.w"], self.w["conv_in.bias"], residual=None if pose is None else pose[:hf], out=x2[:hf])
+            x2[hf:].copy_(x)                            # (one half-tensor copy; torch.cat would read and write both halves)
         else:
             x = hip.conv3x3(x, self.w["conv_in.w"], self.w["conv_in.bias"], residual=pose)
         audio = None
@@ -964,9 +990,9 @@ class UNet3DConditionModel:
             for j in range(lpb):
                 if shared and i == 0 and j == 0:
                     r = f"{p}.resnets.0"
-                    x2 = torch.empty((2 * f,) + tuple(x.shape[1:3]) + (self.spec[r + ".conv1.weight"][0],), device=self._device, dtype=self._dtype)
-                    x = self._resnet(r, x, {r: temb[r][:1]}, out=x2[:f], reader=f"{p}.attentions.0.norm" if self._twin else None)
-                    x2[f:].copy_(x)
+                    x2 = torch.empty((2 * hf,) + tuple(x.shape[1:3]) + (self.spec[r + ".conv1.weight"][0],), device=self._device, dtype=self._dtype)
+                    x = self._resnet(r, x, {r: temb[r][:1]}, out=x2[:hf], reader=f"{p}.attentions.0.norm" if self._twin else None)
+                    x2[hf:].copy_(x)
                     x = x2
                 else:
                     x = self._resnet(f"{p}.resnets.{j}", x, temb, reader=f"{p}.attentions.{j}.norm" if i < 3 else None)

@@ -50,6 +50,7 @@ def parse_args():
     p.add_argument("--steps", type=int, default=30)
     p.add_argument("--fps", type=int)
     p.add_argument("--num_c", type=int, default=12, help="context frames per window")
+    p.add_argument("--context_batch_size", type=int, default=1, help="context windows per UNet forward (the same sampler as 1)")
     p.add_argument("--use_motion_selection", default=False, action="store_true")
     p.add_argument("--num_epoch", type=int, default=3400)
     p.add_argument("--feature_type", type=str, default="wavlm")
@@ -234,7 +235,8 @@ def main():
         ref_img = Image.fromarray(((hash_uniform("a2v.ref", (a.H, a.W, 3), 0.5) + 0.5) * 255).clamp(0, 255).to(torch.uint8).numpy())
     t0 = time.time()
     out = pipe(ref_img, pose, audio_tensor.float(), full, face, lips, a.W, a.H, a.L, a.steps, a.cfg,
-               generator=torch.manual_seed(a.seed), motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c, output_type="uint8")
+               generator=torch.manual_seed(a.seed), motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c,
+               context_batch_size=a.context_batch_size, output_type="uint8")
     torch.cuda.synchronize()
     timing["stage2_s"] = round(time.time() - t0, 3)
     v = torch.as_tensor(out.videos)                                                                          # (1, L, H, W, 3) uint8
@@ -250,7 +252,7 @@ def main():
     else:
         save_videos_grid(v, path, n_rows=1, fps=a.fps or 25)
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
-                      "dtype": a.dtype, "keypoints_finite": bool(np.isfinite(kps).all()),
+                      "dtype": a.dtype, "context_batch_size": a.context_batch_size, "keypoints_finite": bool(np.isfinite(kps).all()),
                       "mask_levels": [list(m.shape) for m in face], **timing, **extra}))
 
 

@@ -43,6 +43,7 @@ def parse_args():
     p.add_argument("--seed", type=int, default=42)
     p.add_argument("--fps", type=int, default=25)
     p.add_argument("--num_c", type=int, default=12, help="context frames per window")
+    p.add_argument("--context_batch_size", type=int, default=1, help="context windows per UNet forward (the same sampler as 1)")
     p.add_argument("--steps", type=int, default=30)          # animation.yaml:28
     p.add_argument("--cfg", type=float, default=3.5)         # animation.yaml:29
     p.add_argument("--synthetic", action="store_true")
@@ -162,7 +163,8 @@ def run_files(a, dev, dtype):
     torch.cuda.synchronize()
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, L, a.steps, a.cfg, generator=gen, motion_scale=[1.0, 1.0, 2.0],
-               context_frames=a.num_c, output_type="jpeg" if a.format == "avi" else "uint8", jpeg_quality=a.quality)
+               context_frames=a.num_c, context_batch_size=a.context_batch_size, output_type="jpeg" if a.format == "avi" else "uint8",
+               jpeg_quality=a.quality)
     torch.cuda.synchronize()
     dt = time.time() - t0
     save_dir = os.path.join(a.out_dir, f"multi_person_{a.num_c}")
@@ -176,7 +178,8 @@ def run_files(a, dev, dtype):
         save_videos_grid(out.videos, path, n_rows=1, fps=a.fps)
         shape = list(torch.as_tensor(out.videos).shape)
     print(json.dumps({"video": shape, "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
-                      "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype, **extra}))
+                      "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype,
+                      "context_batch_size": a.context_batch_size, **extra}))
 
 
 def main():
@@ -223,7 +226,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, a.L, a.steps, a.cfg, generator=gen,
-               motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c, output_type="uint8" if a.clip_parallel else "tensor",
+               motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c, context_batch_size=a.context_batch_size,
+               output_type="uint8" if a.clip_parallel else "tensor",
                decode=not a.no_decode,                         # CLIP embedding and ref_image_latents: HIP encoders, from ref_img
                window_group=True if a.window_parallel else None)
     torch.cuda.synchronize()
@@ -248,7 +252,8 @@ def main():
     torch.save(v if torch.is_tensor(v) else torch.from_numpy(v), path)
     print(json.dumps({"video": list(v.shape), "saved": path, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "windows_per_step": len(list(__import__("mmgt_amd.context", fromlist=["uniform"]).uniform(
-                          0, a.steps, a.L, a.num_c, 1, 4))), "dtype": a.dtype, "finite": bool(torch.as_tensor(v).isfinite().all())}))
+                          0, a.steps, a.L, a.num_c, 1, 4))), "context_batch_size": a.context_batch_size, "dtype": a.dtype,
+                      "finite": bool(torch.as_tensor(v).isfinite().all())}))
 
 
 if __name__ == "__main__":
