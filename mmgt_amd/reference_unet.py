@@ -43,29 +43,25 @@ class UNet2DConditionModel(UNet3DConditionModel):
         for i in range(4):
             p = f"down_blocks.{i}"
             for j in range(lpb):
-                x = self._resnet(f"{p}.resnets.{j}", x, temb)
+                x, _ = self._resnet(f"{p}.resnets.{j}", x, temb)
                 if i < 3:
                     x = self._spatial_transformer(f"{p}.attentions.{j}", x, ehs, 1, write=bank)
                 skips.append(x)
             if i != 3:
                 x = hip.conv3x3(x, self.w[f"{p}.downsamplers.0.conv.w"], self.w[f"{p}.downsamplers.0.conv.bias"], stride=2)
                 skips.append(x)
-        x = self._resnet("mid_block.resnets.0", x, temb)
+        x, _ = self._resnet("mid_block.resnets.0", x, temb)
         mid: Dict[str, torch.Tensor] = {}
         x = self._spatial_transformer("mid_block.attentions.0", x, ehs, 1, write=mid)
-        x = self._resnet("mid_block.resnets.1", x, temb)
+        x, _ = self._resnet("mid_block.resnets.1", x, temb)
         for i in range(4):
             p = f"up_blocks.{i}"
             for j in range(lpb + 1):
-                x = self._resnet(f"{p}.resnets.{j}", x, temb, skip=skips.pop())
+                x, _ = self._resnet(f"{p}.resnets.{j}", x, temb, skip=skips.pop())
                 if i > 0:
                     x = self._spatial_transformer(f"{p}.attentions.{j}", x, ehs, 1, write=bank)
             if i != 3:
-                w2 = self.w.get(f"{p}.upsamplers.0.conv.w2")          # (the four-phase form: unet3d.py `_pack`)
-                if w2 is not None:
-                    x = hip.conv3x3(x, w2, self.w[f"{p}.upsamplers.0.conv.bias"], upsample=2)
-                else:
-                    x = hip.conv3x3(x, self.w[f"{p}.upsamplers.0.conv.w"], self.w[f"{p}.upsamplers.0.conv.bias"], upsample=True)
+                x = self._upsample(f"{p}.upsamplers.0.conv", x)
         bank.update(mid)                              # module order down -> up -> mid
         self.bank = bank
         out = hip.nhwc_to_ncfhw(x, b, self.boc[0])[:, :, 0].to(sample.dtype)

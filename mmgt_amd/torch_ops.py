@@ -221,6 +221,8 @@ def gn_silu_conv3x3(x: torch.Tensor, skip: Optional[torch.Tensor], gamma: torch.
     if not hip.gn_silu_conv3x3_unet_supported(x.dtype, c0, c1, cout, h, w):
         raise RuntimeError(f"mmgt_hip::gn_silu_conv3x3: built for bf16, H and W multiples of 16, channel counts multiples of 64, Cout a multiple of 160 "
                            f"(got {x.dtype}, {h} x {w}, {c0} + {c1} -> {cout})")
+    if temb is not None and (temb.shape[0] == 0 or nb % temb.shape[0]):
+        raise RuntimeError(f"mmgt_hip::gn_silu_conv3x3: temb holds one row per batch entry, so its {temb.shape[0]} rows must divide the {nb} images")
     sc, sh = hip.groupnorm_affine(x.view(nb, h * w, c0), gamma, beta, groups, eps, x1=None if skip is None else skip.view(nb, h * w, c1))
     return hip.gn_silu_conv3x3_unet(x, sc, sh, wimg, cout, bias, temb, 0 if temb is None else nb // temb.shape[0], residual, x1=skip)
 

@@ -38,6 +38,9 @@ class UNet3DConditionOutput:
         return (self.sample,)[i]
 
 
+RCONV_LEVEL = {320: 1, 640: 2, 1280: 4}     # resnet width -> its bit in the `rconv` switch
+
+
 class _Config(dict):
     __getattr__ = dict.__getitem__
 
@@ -138,10 +141,9 @@ class UNet3DConditionModel:
         self._sc_cat = bool(hip.tune_get("sc_cat"))               # a resnet's conv_shortcut over [x | skip] as one two-source launch (0: two GEMMs)
         self._up2 = bool(hip.tune_get("up2"))                     # the up-sampling convs as four 2 x 2 convs on the stored image (0: the 3 x 3 conv on the upsampled view)
         self._fuse_tleg = bool(hip.tune_get("tleg"))              # 0: a level-0 temporal-attention leg as three launches
-        self._tables = None                                       # (reader key, data_ptr, images, (scale, shift)): GroupNorm tables handed from a conv's epilogue to the norm's reader
         self._rconv_stats = bool(hip.tune_get("rconv_stats"))     # a fused leg's output statistics from its epilogue instead of a pass over the tensor
         self._rconv = hip.tune_get("rconv")                        # resnets whose GroupNorm -> SiLU -> conv3x3 legs run as one launch (csrc/rconv.hip): a mask of
-                                                                   # 1 the 320-wide level, 2 the 640-wide level, 4 the 1280-wide level (16 x 16 pixel tiles)
+                                                                   # RCONV_LEVEL's bits (16 x 16 pixel tiles)
         self.spec = unet3d_spec(boc, cfg["cross_attention_dim"], cfg["audio_attention_dim"], self.in_channels,
                                 self.out_channels, cfg["layers_per_block"],
                                 cfg["motion_module_kwargs"].get("temporal_position_encoding_max_len", 32))
@@ -252,6 +254,8 @@ class UNet3DConditionModel:
         self._zbias = {}
         self._ffpo = {}
         self._banks = {}
+        for k in [k for k in self.w if k.endswith(".rimg")]:     # images of the previous weights (`_rimg` builds them on first use)
+            del self.w[k]
         return missing, unexpected
 
     def _t(self, x):      # model-dtype device copy
@@ -336,12 +340,6 @@ class UNet3DConditionModel:
             conv(p + ".conv1")
             conv(p + ".conv2")
             cout = self.spec[p + ".conv1.weight"][0]
-            if self._dtype == torch.bfloat16 and (self._rconv & {320: 1, 640: 2, 1280: 4}.get(cout, 0)) and \
-                    has(p + ".conv1.weight") and has(p + ".conv2.weight"):
-                for cv in (".conv1", ".conv2"):                        # fragment-major images of the fused GroupNorm + SiLU + conv launch
-                    wt = sd[p + cv + ".weight"]
-                    if hip.gn_silu_conv3x3_unet_supported(self._dtype, wt.shape[1], 0, wt.shape[0], 16, 16):
-                        w[p + cv + ".rimg"] = pack_rconv(wt.to(self._device))
             self._temb_slices[p] = (off, cout)
             off += cout
             if has(p + ".time_emb_proj.weight"):
@@ -513,19 +511,23 @@ class UNet3DConditionModel:
                                 self.w[p + ".ff2.w"].shape[1])
         return self._ff(p, self._ln(norm, hid), hid)
 
-    def _norm_proj_in(self, p, x):
+    def _proj_in_fused(self, p, n):
+        """Whether transformer block `p` runs GroupNorm -> proj_in over n tokens per image as the one-launch form of `_norm_proj_in`; `_resnet` asks
+        it before it has conv2 produce that norm's tables (a fused leg's pixels tile into 16 x 16: n % 256 == 0 there, so only n > 256 decides)."""
+        return (p + ".proj_in.img") in self.w and n > 256 and n % 128 == 0
+
+    def _norm_proj_in(self, p, x, tables=None):
         """proj_in(GroupNorm(x)) of a transformer block (transformer_3d.py:174-188, motion_module.py:156-170) -> (nb*h*w, inner): at the
-        320-channel level the statistics pass alone, then one launch that normalises the rows while it loads them (csrc/rowgemm.hip)."""
+        320-channel level the statistics pass alone, then one launch that normalises the rows while it loads them (csrc/rowgemm.hip).
+        tables: (scale, shift) of this norm for x from the epilogue of the conv that wrote x (`_resnet`, reader=), or None."""
         nb, h, ww, c = x.shape
         n = h * ww
-        img = self.w.get(p + ".proj_in.img")
-        if img is not None and n > 256 and n % 128 == 0:
-            kept, self._tables = self._tables, None
-            if kept is not None and kept[0] == p + ".norm" and kept[1] == x.data_ptr() and kept[2] == nb:
-                sc, sh = kept[3]          # from the epilogue of the conv that wrote x (`_resnet`, reader=)
+        if self._proj_in_fused(p, n):
+            if tables is not None and tables[0].shape == (nb, c):
+                sc, sh = tables
             else:
                 sc, sh = hip.groupnorm_affine(x.view(nb, n, c), self.w[p + ".norm.g"], self.w[p + ".norm.b"], 32, 1e-6)
-            return hip.rowgemm320(x.view(nb * n, c), img, self.w[p + ".proj_in.w"].shape[0], self.w.get(p + ".proj_in.bias"),
+            return hip.rowgemm320(x.view(nb * n, c), self.w[p + ".proj_in.img"], self.w[p + ".proj_in.w"].shape[0], self.w.get(p + ".proj_in.bias"),
                                   pre_scale=sc, pre_shift=sh, pre_rows=n)[0]
         xn = self._gn(p + ".norm", x, 1e-6)
         return self._lin(p + ".proj_in", xn.view(nb * n, c))
@@ -564,25 +566,25 @@ class UNet3DConditionModel:
         return self._ffpo[key]
 
     def _resnet(self, p, x, temb, skip=None, out=None, reader=None):
-        """ResnetBlock3D (resnet.py:217-247); `skip` = the UNet skip tensor that the reference concatenates first.  reader: key of the
-        GroupNorm that reads the result next (a transformer block's `norm`): on the fused path its tables come out of conv2's epilogue
-        (`_norm_proj_in` picks them up from self._tables)."""
+        """ResnetBlock3D (resnet.py:217-247); `skip` = the UNet skip tensor that the reference concatenates first.  reader: the transformer
+        block that reads the result next.  Returns (y, tables): on the fused path the (scale, shift) of the reader's `norm` for y come out of
+        conv2's epilogue where the reader takes them (`_norm_proj_in`); None otherwise."""
         nb, h, ww, c0 = x.shape
         hw = h * ww
         cout = self.spec[p + ".conv1.weight"][0]
         c1 = 0 if skip is None else skip.shape[3]
         # GroupNorm-apply + SiLU + conv3x3 as ONE launch behind the statistics pass (csrc/rconv.hip): the normalised tensor is never written
-        fused = (p + ".conv1.rimg") in self.w and (p + ".conv2.rimg") in self.w and \
+        fused = bool(self._rconv & RCONV_LEVEL.get(cout, 0)) and \
             hip.gn_silu_conv3x3_unet_supported(self._dtype, c0, c1, cout, h, ww) and hip.gn_silu_conv3x3_unet_supported(self._dtype, cout, 0, cout, h, ww)
         if fused:
             eps = self.config.norm_eps
             sc, sh = hip.groupnorm_affine(x.view(nb, hw, c0), self.w[p + ".norm1.g"], self.w[p + ".norm1.b"], 32, eps,
                                           x1=None if skip is None else skip.view(nb, hw, c1))
             if self._rconv_stats:       # norm2's statistics from conv1's epilogue (resnet.py:231): no pass over the tensor
-                hdn, (sc, sh) = hip.gn_silu_conv3x3_unet(x, sc, sh, self.w[p + ".conv1.rimg"], cout, self.w[p + ".conv1.bias"], temb[p], nb // temb[p].shape[0],
+                hdn, (sc, sh) = hip.gn_silu_conv3x3_unet(x, sc, sh, self._rimg(p, ".conv1"), cout, self.w[p + ".conv1.bias"], temb[p], nb // temb[p].shape[0],
                                                          x1=skip, next_norm=(self.w[p + ".norm2.g"], self.w[p + ".norm2.b"], 32, eps))
             else:
-                hdn = hip.gn_silu_conv3x3_unet(x, sc, sh, self.w[p + ".conv1.rimg"], cout, self.w[p + ".conv1.bias"], temb[p], nb // temb[p].shape[0], x1=skip)
+                hdn = hip.gn_silu_conv3x3_unet(x, sc, sh, self._rimg(p, ".conv1"), cout, self.w[p + ".conv1.bias"], temb[p], nb // temb[p].shape[0], x1=skip)
                 sc, sh = hip.groupnorm_affine(hdn.view(nb, hw, cout), self.w[p + ".norm2.g"], self.w[p + ".norm2.b"], 32, eps)
         else:
             hdn = self._gn(p + ".norm1", x, self.config.norm_eps, silu=True, x1=skip)
@@ -608,13 +610,26 @@ class UNet3DConditionModel:
             assert skip is None
             res = x
         if fused:
-            if reader is not None and self._rconv_stats and hw > 256 and (reader.rsplit(".", 1)[0] + ".proj_in.img") in self.w:
-                y, tab = hip.gn_silu_conv3x3_unet(hdn, sc, sh, self.w[p + ".conv2.rimg"], cout, self.w[p + ".conv2.bias"], residual=res, out=out,
-                                                  next_norm=(self.w[reader + ".g"], self.w[reader + ".b"], 32, 1e-6))
-                self._tables = (reader, y.data_ptr(), nb, tab)
-                return y
-            return hip.gn_silu_conv3x3_unet(hdn, sc, sh, self.w[p + ".conv2.rimg"], cout, self.w[p + ".conv2.bias"], residual=res, out=out)
-        return hip.conv3x3(hdn, self.w[p + ".conv2.w"], self.w[p + ".conv2.bias"], residual=res, out=out)
+            if reader is not None and self._rconv_stats and self._proj_in_fused(reader, hw):
+                return hip.gn_silu_conv3x3_unet(hdn, sc, sh, self._rimg(p, ".conv2"), cout, self.w[p + ".conv2.bias"], residual=res, out=out,
+                                                next_norm=(self.w[reader + ".norm.g"], self.w[reader + ".norm.b"], 32, 1e-6))
+            return hip.gn_silu_conv3x3_unet(hdn, sc, sh, self._rimg(p, ".conv2"), cout, self.w[p + ".conv2.bias"], residual=res, out=out), None
+        return hip.conv3x3(hdn, self.w[p + ".conv2.w"], self.w[p + ".conv2.bias"], residual=res, out=out), None
+
+    def _rimg(self, p, cv):
+        """The fragment-major image of a fused leg's conv (csrc/rconv.hip), built on first use from the stored [Cout][3][3][Cin] weight: that was
+        rounded to bf16 once and the image only permutes, so it is bit for bit the image of the checkpoint tensor."""
+        key = p + cv + ".rimg"
+        if key not in self.w:
+            self.w[key] = pack_rconv(self.w[p + cv + ".w"].permute(0, 3, 1, 2))
+        return self.w[key]
+
+    def _upsample(self, p, x):
+        """Upsample3D (resnet.py:31-77): nearest 2x, then the 3 x 3 conv -- as four 2 x 2 convs on the stored image where `.w2` exists (`_pack`)."""
+        w2 = self.w.get(p + ".w2")
+        if w2 is not None:
+            return hip.conv3x3(x, w2, self.w[p + ".bias"], upsample=2)
+        return hip.conv3x3(x, self.w[p + ".w"], self.w[p + ".bias"], upsample=True)
 
     def _sc_split(self, p, c0, which):
         key = f"{p}.sc.w.{which}"
@@ -655,14 +670,14 @@ class UNet3DConditionModel:
                       v_str=(inner * npad, 0, npad), o_str=(n * inner, 0, inner), v_transposed=True, **kw)
         return o
 
-    def _spatial_transformer(self, p, x, ehs, frames, write=None, cfg_row=None):
+    def _spatial_transformer(self, p, x, ehs, frames, write=None, cfg_row=None, tables=None):
         """Transformer3DModel + TemporalBasicTransformerBlock in bank-read mode (transformer_3d.py:139-268,
         mutual_self_attention.py:149-230)."""
         nb, h, ww, c = x.shape
         n = h * ww
         m = nb * n
         t = p + ".transformer_blocks.0"
-        hid = self._norm_proj_in(p, x)
+        hid = self._norm_proj_in(p, x, tables)
         inner = hid.shape[1]
         fuse = write is None and (t + ".attn1.qkv_img") in self.w and n % 128 == 0
         n1 = hid if fuse else self._ln(t + ".norm1", hid)
@@ -684,7 +699,7 @@ class UNet3DConditionModel:
         out = self._norm_ff_proj_out(t + ".ff", t + ".norm3", hid, p, x.view(m, c))
         return out.view(nb, h, ww, c)
 
-    def _spatial_transformer_twin(self, p, x2, ehs, frames):
+    def _spatial_transformer_twin(self, p, x2, ehs, frames, tables=None):
         """The first reference-attention reader of a CFG pair whose rows entered with the same input (`cfg_rows_share_input`): x2 =
         ((2 f), h, w, c) with identical halves.  GroupNorm, proj_in, LayerNorm and q | k | V^T are computed for the f frames once; ONE
         attention pass over the frames' own keys serves both rows -- the unconditional row's output [x] is the state of the conditional
@@ -700,7 +715,7 @@ class UNet3DConditionModel:
         if bank is None or (t + ".attn1.qkv_img") not in self.w or ehs.shape[1] != 1 or self._dtype != torch.bfloat16 or hd != 40 \
                 or n % 256 or bank[2] % 64 or nb % 2:
             return None
-        hid = self._norm_proj_in(p, x2[:f])                                              # (f n, inner)
+        hid = self._norm_proj_in(p, x2[:f], tables)                                              # (f n, inner)
         npad = round_up(n, 8)
         vt = torch.empty((f, inner, npad), device=self._device, dtype=self._dtype)
         qk, _ = hip.rowgemm320(hid, self.w[t + ".attn1.qkv_img"], 3 * inner, ln_gamma=self.w[t + ".norm1.g"], ln_beta=self.w[t + ".norm1.b"],
@@ -991,14 +1006,14 @@ class UNet3DConditionModel:
                 if shared and i == 0 and j == 0:
                     r = f"{p}.resnets.0"
                     x2 = torch.empty((2 * hf,) + tuple(x.shape[1:3]) + (self.spec[r + ".conv1.weight"][0],), device=self._device, dtype=self._dtype)
-                    x = self._resnet(r, x, {r: temb[r][:1]}, out=x2[:hf], reader=f"{p}.attentions.0.norm" if self._twin else None)
+                    x, tab = self._resnet(r, x, {r: temb[r][:1]}, out=x2[:hf], reader=f"{p}.attentions.0" if self._twin else None)
                     x2[hf:].copy_(x)
                     x = x2
                 else:
-                    x = self._resnet(f"{p}.resnets.{j}", x, temb, reader=f"{p}.attentions.{j}.norm" if i < 3 else None)
+                    x, tab = self._resnet(f"{p}.resnets.{j}", x, temb, reader=f"{p}.attentions.{j}" if i < 3 else None)
                 if i < 3:
-                    y = self._spatial_transformer_twin(f"{p}.attentions.{j}", x, ehs, f) if (shared and i == 0 and j == 0 and self._twin) else None
-                    x = y if y is not None else self._spatial_transformer(f"{p}.attentions.{j}", x, ehs, f, cfg_row=cfg_row)
+                    y = self._spatial_transformer_twin(f"{p}.attentions.{j}", x, ehs, f, tab) if (shared and i == 0 and j == 0 and self._twin) else None
+                    x = y if y is not None else self._spatial_transformer(f"{p}.attentions.{j}", x, ehs, f, cfg_row=cfg_row, tables=tab)
                     if f"{p}.audio_modules.{j}" in self._audio:
                         x = self._audio_transformer(f"{p}.audio_modules.{j}", x, audio, masks, i, ms, ms_cache)
                 x = self._motion_module(f"{p}.motion_modules.{j}", x, f)
@@ -1007,24 +1022,20 @@ class UNet3DConditionModel:
                 x = hip.conv3x3(x, self.w[f"{p}.downsamplers.0.conv.w"], self.w[f"{p}.downsamplers.0.conv.bias"], stride=2)
                 skips.append(x)
 
-        x = self._resnet("mid_block.resnets.0", x, temb)
+        x, _ = self._resnet("mid_block.resnets.0", x, temb)
         x = self._spatial_transformer("mid_block.attentions.0", x, ehs, f, cfg_row=cfg_row)
         x = self._motion_module("mid_block.motion_modules.0", x, f)
-        x = self._resnet("mid_block.resnets.1", x, temb)
+        x, _ = self._resnet("mid_block.resnets.1", x, temb)
 
         for i in range(4):
             p = f"up_blocks.{i}"
             for j in range(lpb + 1):
-                x = self._resnet(f"{p}.resnets.{j}", x, temb, skip=skips.pop(), reader=f"{p}.attentions.{j}.norm" if i > 0 else None)
+                x, tab = self._resnet(f"{p}.resnets.{j}", x, temb, skip=skips.pop(), reader=f"{p}.attentions.{j}" if i > 0 else None)
                 if i > 0:
-                    x = self._spatial_transformer(f"{p}.attentions.{j}", x, ehs, f, cfg_row=cfg_row)
+                    x = self._spatial_transformer(f"{p}.attentions.{j}", x, ehs, f, cfg_row=cfg_row, tables=tab)
                 x = self._motion_module(f"{p}.motion_modules.{j}", x, f)
             if i != 3:
-                w2 = self.w.get(f"{p}.upsamplers.0.conv.w2")
-                if w2 is not None:
-                    x = hip.conv3x3(x, w2, self.w[f"{p}.upsamplers.0.conv.bias"], upsample=2)
-                else:
-                    x = hip.conv3x3(x, self.w[f"{p}.upsamplers.0.conv.w"], self.w[f"{p}.upsamplers.0.conv.bias"], upsample=True)
+                x = self._upsample(f"{p}.upsamplers.0.conv", x)
 
         timg = self.w.get("conv_out.timg")
         nb, h, ww, c = x.shape

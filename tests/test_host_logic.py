@@ -192,6 +192,17 @@ def test_pack_rconv_fragment_image():
     assert hip.lib().mmgt_gn_silu_conv3x3_unet_image_bytes(320, 300) == -1
 
 
+def test_pack_rconv_from_the_stored_conv_weight_is_the_image_of_the_checkpoint_tensor():
+    """`UNet3DConditionModel._rimg` builds a fused leg's image on first use from the stored `.w` (pack_conv3x3, rounded to bf16 once) instead of
+    the fp32 checkpoint tensor: pack_rconv rounds first and then only permutes, so the two images are the same bytes."""
+    from mmgt_amd.packing import pack_conv3x3, pack_rconv
+    from mmgt_amd.synthetic import hash_uniform
+    for cout, cin in ((320, 320), (320, 640), (1280, 2560)):            # the last two: the widest skip-concat legs of their levels
+        w = hash_uniform(f"rimg.{cout}.{cin}.weight", (cout, cin, 3, 3), (9 * cin) ** -0.5)
+        stored = pack_conv3x3(w).to(torch.bfloat16)
+        assert torch.equal(pack_rconv(w), pack_rconv(stored.permute(0, 3, 1, 2)))
+
+
 def test_pack_gnconv_fragment_image():
     """The weight image of csrc/gnconv.hip: [block of <= 128 output channels][128-channel phase][tap][k-step of 32][16-channel tile][lane][8] with
     lane (lm, lq) = row lm of the tile, reduction slots 8 lq .. 8 lq + 7 -- checked entry by entry against the definition."""
@@ -277,6 +288,16 @@ def test_product_never_imports_the_oracle():
             if f.endswith(".py"):
                 src = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(from|import)\s+oracle", src, re.M), f
+
+
+def test_product_hands_groupnorm_tables_over_explicitly():
+    """The tables of a fused conv's epilogue travel as a return value and an argument (`_resnet` -> `_norm_proj_in`), never as state on the
+    model; the VAE has no reader to name to a launch."""
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "mmgt_amd")):
+        for f in files:
+            if f.endswith(".py"):
+                src = open(os.path.join(dirpath, f)).read()
+                assert not re.search(r"(?<!\w)_tables\b|\bnext_pn\b", src), f      # the identifiers, not `gn_silu_conv3x3_tables` and its like
 
 
 # ------------------------------------------------------------------------------------------------ multi-process (gloo)

@@ -167,6 +167,23 @@ def test_fused_projection_ops_match_torch_math_bf16():
 
 
 @pytest.mark.gpu
+def test_gn_silu_conv3x3_op_refuses_temb_rows_that_do_not_divide_the_images():
+    """5 images against a 2-row temb: a RuntimeError that names both, raised before anything is launched."""
+    from mmgt_amd import hip
+    from mmgt_amd.packing import pack_rconv
+    r = lambda name, shape, s=1.0: hash_uniform("ops." + name, shape, s).cuda()
+    nb, hh, c, rows = 5, 16, 320, 2
+    x = r("rt.x", (nb, hh, hh, c)).bfloat16()
+    wimg = pack_rconv(r("rt.w", (c, c, 3, 3), 0.02))
+    before = dict(hip._calls)
+    with pytest.raises(RuntimeError, match=r"(?s)\b2 rows.*\b5 images"):
+        torch.ops.mmgt_hip.gn_silu_conv3x3(x, None, torch.ones(c).cuda(), torch.zeros(c).cuda(), 32, 1e-5, wimg, c, None, r("rt.te", (rows, c)), None)
+    with pytest.raises(RuntimeError, match=r"(?s)\b0 rows.*\b5 images"):
+        torch.ops.mmgt_hip.gn_silu_conv3x3(x, None, torch.ones(c).cuda(), torch.zeros(c).cuda(), 32, 1e-5, wimg, c, None, r("rt.te", (rows, c))[:0], None)
+    assert hip._calls == before
+
+
+@pytest.mark.gpu
 def test_vae_decode_op_matches_oracle():
     from mmgt_amd.synthetic import synth_state_dict
     from mmgt_amd.vae import vae_decoder_spec

@@ -278,6 +278,78 @@ def test_groupnorm_tables_from_conv_epilogues_512x512_six_frames(full_sd, golden
     assert d.mean() <= fmean
 
 
+FUSED_BLOCKS = ("down_blocks.0.", "down_blocks.2.", "up_blocks.1.", "up_blocks.3.")    # 64 x 64 and 16 x 16 pixels, 320 and 1280 wide: 10 resnets
+
+
+def _rimg_keys(model):
+    return {k for k in model.w if k.endswith(".rimg")}
+
+
+def _fused_leg_keys(model):
+    return {r + cv + ".rimg" for r in model._resnets if r.startswith(FUSED_BLOCKS) for cv in (".conv1", ".conv2")}
+
+
+def _six_frame_model(sd_gpu):
+    from mmgt_amd.unet3d import UNet3DConditionModel
+    m = UNet3DConditionModel(device="cuda:0", dtype=torch.bfloat16)
+    m.load_state_dict(sd_gpu)
+    m.enable_gradient_checkpointing()
+    inp = _to_dev(gc.unet_inputs(SIX_FRAME_CASE))
+    m.set_banks(inp["banks"])
+    run = lambda: m(inp["sample"], inp["timestep"], encoder_hidden_states=inp["ehs"], audio_embedding=inp["audio"], pose_cond_fea=inp["pose"],
+                    full_mask=inp["full"], face_mask=inp["face"], body_mask=inp["lips"], motion_scale=inp["motion_scale"], return_dict=False)[0]
+    return m, run
+
+
+def test_fused_leg_images_exist_where_a_forward_read_them_512x512_six_frames(full_sd):
+    """The weight images of the fused GroupNorm -> SiLU -> conv3x3 legs (csrc/rconv.hip) are built by the first forward that runs the leg: none
+    after load_state_dict, then conv1 and conv2 of exactly the ten resnets whose level is in the `rconv` mask and whose pixels tile into
+    16 x 16 (the 8 x 8 level never does at 64 x 64 latents), one fused launch each; a second forward builds nothing and repeats the first bit
+    for bit; a repeated load drops the images of the previous weights."""
+    from mmgt_amd import hip
+    sd_gpu, _ = full_sd
+    m, run = _six_frame_model(sd_gpu)
+    assert not _rimg_keys(m)
+    n0 = hip.call_count("mmgt_gn_silu_conv3x3_unet")
+    first = run()
+    launches = hip.call_count("mmgt_gn_silu_conv3x3_unet") - n0
+    want = _fused_leg_keys(m)
+    assert len(want) == 20 and _rimg_keys(m) == want
+    assert launches == 20, f"{launches} fused launches in one forward (20 expected: 10 resnets x 2 legs)"
+    assert torch.equal(run(), first) and _rimg_keys(m) == want
+    m.load_state_dict(sd_gpu)
+    assert not _rimg_keys(m)
+
+
+def test_fused_leg_switched_off_builds_no_image(full_sd):
+    """`rconv` = 0, read once by the constructor: no fused launch and no image."""
+    from mmgt_amd import hip
+    sd_gpu, _ = full_sd
+    mask = hip.tune_get("rconv")
+    try:
+        hip.tune("rconv", 0)
+        m, run = _six_frame_model(sd_gpu)
+    finally:
+        hip.tune("rconv", mask)
+    n0 = hip.call_count("mmgt_gn_silu_conv3x3_unet")
+    assert torch.isfinite(run()).all()
+    assert hip.call_count("mmgt_gn_silu_conv3x3_unet") == n0 and not _rimg_keys(m)
+
+
+def test_reference_net_builds_fused_leg_images_for_its_fused_resnets_only():
+    """The ReferenceNet shares the UNet's blocks: after `write_banks` at 64 x 64 latents its images are those of the same ten resnets."""
+    from mmgt_amd.reference_unet import UNet2DConditionModel
+    from mmgt_amd.synthetic import hash_uniform
+    from mmgt_amd.unet3d_spec import unet2d_reference_spec
+    m = UNet2DConditionModel(device="cuda:0", dtype=torch.bfloat16)
+    m.load_state_dict(synth_state_dict(unet2d_reference_spec(), device="cuda:0"))
+    assert not _rimg_keys(m)
+    bank = m.write_banks(hash_uniform("refnet.lat", (2, 4, 64, 64), 1.0).cuda(), 0, hash_uniform("refnet.ehs", (2, 1, 768), 1.0).cuda())
+    assert len(bank) == 16 and all(torch.isfinite(v).all() for v in bank.values())
+    want = _fused_leg_keys(m)
+    assert len(want) == 20 and _rimg_keys(m) == want
+
+
 TWELVE_FRAME_CASE = dict(gc.UNET_CASES["full_cfg1"], frames=12, latent=64, timestep=499)
 
 

@@ -164,7 +164,8 @@ def test_hip_vae_full_resolution_frame():
     """One 512x512 frame (64x64 latent) in bf16: the size the sampler decodes (pipeline_pose2vid_long.py:112-125), against the ORACLE's decode of
     the same latent at the bf16 gate in all three forms of the GroupNorm -> SiLU -> conv legs -- only a full-resolution frame has `gnconv`
     tiles in the interior, on every edge and many tiles per workgroup, the statistics chain across its 12 launches and the two-launch
-    256-wide split -- and through frame independence."""
+    256-wide split -- and through frame independence.  The 512-channel levels run as `groupnorm` + `conv3x3` in every form (csrc/rconv.hip
+    serves the UNet's 320- and 1280-wide levels only)."""
     from tests.oracle_cache import cached
     from mmgt_amd.vae import AutoencoderKL
     vae = AutoencoderKL(device="cuda:0", dtype=torch.bfloat16)
@@ -202,6 +203,21 @@ def test_hip_vae_full_resolution_frame():
         assert d.max() <= 5e-2 and d.mean() <= 3e-3, (d.max().item(), d.mean().item())
         torch.testing.assert_close(other[:, :, 1:2].cpu(), ref, rtol=0, atol=4e-2)          # each form against the oracle, not only against each other
     assert torch.equal(both, vae.decode_video(lat, frames_per_batch=2))                      # repeatable
+
+
+@pytest.mark.gpu
+def test_hip_vae_never_runs_the_unet_fused_leg():
+    """csrc/rconv.hip cuts its output into blocks of 320 / 256 / 160 channels of a multiple of 160: the decoder's 512- and 256-wide convs are
+    not among them, so the VAE holds no image for that launch and a full-resolution decode never calls it."""
+    from mmgt_amd import hip
+    from mmgt_amd.vae import AutoencoderKL
+    vae = AutoencoderKL(device="cuda:0", dtype=torch.bfloat16)
+    vae.load_state_dict(_sd("cuda:0", encoder=True))
+    assert not any(k.endswith(".rimg") for k in vae.w)
+    n0 = hip.call_count("mmgt_gn_silu_conv3x3_unet")
+    out = vae.decode_video(hash_uniform("vae.lat512", (1, 4, 2, 64, 64), 1.0).cuda()[:, :, 1:2].contiguous(), frames_per_batch=1)
+    assert out.shape == (1, 3, 1, 512, 512) and torch.isfinite(out).all()
+    assert hip.call_count("mmgt_gn_silu_conv3x3_unet") == n0
 
 
 def test_oracle_vae_encoder_known_answers():
