@@ -403,6 +403,27 @@ int mmgt_jpeg_compact(const unsigned char* segs, long seg_stride, const int* siz
                       int nseg, int mcu_rows, void* stream);
 /* Host: the luminance and chrominance quantiser tables of `quality` in zigzag order (the body of two DQT segments), 128 bytes. */
 int mmgt_jpeg_qtables(int quality, unsigned char* zigzag128);
+/* ---- GIF output path (csrc/gif.hip, mmgt_amd/video_out.py): GIF89a image data of device-resident frames with ONE palette for the clip.
+ * A colour's bin is (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) (15 bits).  Every buffer is a device pointer; frames, idx, out are 4-byte aligned, lut
+ * 16-byte aligned.  n, H, W >= 1, H, W <= 65535, n * H * W < 2^32.  Like every entry: 0 on success, else mmgt_last_error() has the text and
+ * nothing was launched.
+ * histogram: frames (n, H, W, 3) u8 RGB -> hist[32768] += pixels per bin (the caller zeroes hist). */
+int mmgt_gif_histogram(const unsigned char* frames, unsigned int* hist, int n, int H, int W, void* stream);
+/* idx (n, H, W) u8 = lut[bin(pixel)], lut u8[32768] (video_out.gif_lut: the nearest palette entry of each bin centre).  No dithering. */
+int mmgt_gif_index(const unsigned char* frames, const unsigned char* lut, unsigned char* idx, int n, int H, int W, void* stream);
+/* GIF LZW (minimum code size 8, codes of 9 .. 12 bits, Clear = 256, End-of-Information = 257) of every (frame, strip): strip s of a frame is its rows
+ * s * strip_rows .. min(H, (s + 1) * strip_rows) - 1, strips = ceil(H / strip_rows) <= 2048.  The strip's bits go LSB-first to
+ * out + (frame * strips + s) * out_stride, their count to bits[frame * strips + s].  Every strip codes with a dictionary of its own: strip 0 opens
+ * with Clear, every strip but the last closes with Clear (written at the width the decoder then holds), the last with End-of-Information, so a
+ * frame's strips concatenated bit by bit are one valid GIF code stream.  out_stride >= strip_stride(W, strip_rows), a multiple of 4: the bound no
+ * input can exceed, 12 (P + floor(P / 3838) + 2) bits for P = W * strip_rows pixels, in bytes rounded up to 16. */
+int mmgt_gif_lzw(const unsigned char* idx, unsigned char* out, long long* bits, int n, int H, int W, int strip_rows, long out_stride, void* stream);
+int mmgt_gif_strip_stride(int W, int strip_rows, long* stride);
+/* Joins the strips of each frame at bit offsets (exclusive prefix sum of bits) and cuts the byte stream into GIF data sub-blocks: frame f's
+ * image data, without the minimum-code-size byte, is packed[f * packed_stride : f * packed_stride + sizes[f]] = { length <= 255, bytes } ... 0x00.
+ * packed_stride >= B + ceil(B / 255) + 1 with B = strips * out_stride. */
+int mmgt_gif_pack(const unsigned char* out, const long long* bits, unsigned char* packed, int* sizes, int n, int strips, long out_stride,
+                  long packed_stride, void* stream);
 /* SMGA key points -> the four frame streams of Stage 2, drawn on the device: kp (frames, 134, 3) fp32 = SMGA's normalised
  * (x, y, score) features.  Replaces data/extract_movment_mask_all.py:319-321 `pose_vid_generator` (denormalize :128-132, mask_leg :66-89,
  * process_keypoints :98-119), src/dwpose/__init__.py:220-283 `DWposeDetector_movment_mask.__call__` with draw_pose / draw_pose_mask_head /

@@ -111,6 +111,11 @@ _SIGS = {
     "mmgt_jpeg_scan": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "mmgt_jpeg_compact": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
     "mmgt_jpeg_qtables": (c_int, [c_int, c_void_p]),
+    "mmgt_gif_histogram": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_gif_index": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_gif_lzw": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p]),
+    "mmgt_gif_strip_stride": (c_int, [c_int, c_int, ctypes.POINTER(c_long)]),
+    "mmgt_gif_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
@@ -1036,6 +1041,86 @@ def jpeg_compact(segs, sizes, mcu_rows):
     _check(lib().mmgt_jpeg_compact(_ptr(segs), segs.shape[1], _ptr(sizes), _ptr(offsets), _ptr(data), total, nseg, int(mcu_rows), _stream()),
            "mmgt_jpeg_compact")
     return data, host
+
+
+# ------------------------------------------------------------------------------------------------------------ GIF (csrc/gif.hip)
+
+GIF_BINS = 32768
+
+
+def _gif_frames(frames, what):
+    _dev(frames)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
+        raise RuntimeError(f"{what}: frames must be contiguous uint8 (n, H, W, 3)")
+    return frames.shape[:3]
+
+
+def gif_histogram(frames):
+    """(n, H, W, 3) uint8 RGB -> (32768,) pixels per 5-bit-per-channel bin (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) of the whole clip, on the
+    device.  The counts are uint32 held in an int32 tensor: read them with .cpu().numpy().view(numpy.uint32)."""
+    n, H, W = _gif_frames(frames, "gif_histogram")
+    hist = torch.zeros((GIF_BINS,), device=frames.device, dtype=torch.int32)
+    _check(lib().mmgt_gif_histogram(_ptr(frames), _ptr(hist), n, H, W, _stream()), "mmgt_gif_histogram")
+    return hist
+
+
+def gif_index(frames, lut):
+    """idx (n, H, W) uint8 = lut[bin(pixel)]; lut (32768,) uint8 on the device."""
+    n, H, W = _gif_frames(frames, "gif_index")
+    _dev(lut)
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (GIF_BINS,) or not lut.is_contiguous():
+        raise RuntimeError("gif_index: lut must be contiguous uint8 (32768,)")
+    idx = torch.empty((n, H, W), device=frames.device, dtype=torch.uint8)
+    _check(lib().mmgt_gif_index(_ptr(frames), _ptr(lut), _ptr(idx), n, H, W, _stream()), "mmgt_gif_index")
+    return idx
+
+
+def gif_strip_stride(W, strip_rows):
+    """Bytes that the LZW bit string of one strip of `strip_rows` rows cannot exceed, whatever the indices (csrc/gif.hip states the bound)."""
+    v = c_long(0)
+    _check(lib().mmgt_gif_strip_stride(int(W), int(strip_rows), ctypes.byref(v)), "mmgt_gif_strip_stride")
+    return v.value
+
+
+def gif_packed_stride(strips, out_stride):
+    """Bytes that one frame's data sub-blocks cannot exceed: its slots' bytes, a length byte per 255 of them and the terminator, rounded up to 16."""
+    b = int(strips) * int(out_stride)
+    return (b + -(-b // 255) + 1 + 15) // 16 * 16
+
+
+def gif_lzw(idx, strip_rows, out=None):
+    """idx (n, H, W) uint8 -> (out (n * strips, stride) uint8, bits (n, strips) int64): the LZW bit string of every (frame, strip), LSB-first, and
+    its length; only the first ceil(bits / 32) words of a row of `out` are written.  `out` = (out, bits) to write into."""
+    _dev(idx)
+    if idx.dtype != torch.uint8 or idx.dim() != 3 or not idx.is_contiguous():
+        raise RuntimeError("gif_lzw: idx must be contiguous uint8 (n, H, W)")
+    n, H, W = idx.shape
+    stride = gif_strip_stride(W, strip_rows)
+    strips = -(-H // int(strip_rows))
+    if out is None:
+        out = (torch.empty((n * strips, stride), device=idx.device, dtype=torch.uint8),
+               torch.empty((n, strips), device=idx.device, dtype=torch.int64))
+    slots, bits = out
+    assert slots.dim() == 2 and slots.shape[0] == n * strips and slots.dtype == torch.uint8 and slots.stride(1) == 1
+    assert bits.shape == (n, strips) and bits.dtype == torch.int64 and bits.is_contiguous()
+    _check(lib().mmgt_gif_lzw(_ptr(idx), _ptr(slots), _ptr(bits), n, H, W, int(strip_rows), slots.stride(0), _stream()), "mmgt_gif_lzw")
+    return slots, bits
+
+
+def gif_pack(slots, bits, out=None):
+    """The strips of gif_lzw -> (packed (n, packed_stride) uint8, sizes (n,) int32): frame f's GIF data sub-blocks with their 0x00 terminator are
+    packed[f, :sizes[f]].  `out` = (packed, sizes) to write into."""
+    _dev(slots, bits)
+    n, strips = bits.shape
+    if out is None:
+        out = (torch.empty((n, gif_packed_stride(strips, slots.stride(0))), device=slots.device, dtype=torch.uint8),
+               torch.empty((n,), device=slots.device, dtype=torch.int32))
+    packed, sizes = out
+    assert packed.dim() == 2 and packed.shape[0] == n and packed.dtype == torch.uint8 and packed.stride(1) == 1
+    assert sizes.shape == (n,) and sizes.dtype == torch.int32
+    _check(lib().mmgt_gif_pack(_ptr(slots), _ptr(bits), _ptr(packed), _ptr(sizes), n, strips, slots.stride(0), packed.stride(0), _stream()),
+           "mmgt_gif_pack")
+    return packed, sizes
 
 
 def dwpose_draw(kp, H=512, W=512):

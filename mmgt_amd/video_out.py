@@ -3,7 +3,9 @@
 csrc/conditioning.hip: mmgt_frames_to_u8); this module only lays frames out and writes them.  The reference's .mp4 branch
 encodes with PyAV / libx264, which is not part of this build: .gif goes through PIL exactly as the reference's .gif branch does,
 .npy stores the raw uint8 frames, .mp4 raises.  .avi is this build's video file: baseline JPEG frames encoded on the device
-(csrc/mjpeg.hip; encode_jpeg_frames) in a RIFF AVI 1.0 container with an optional PCM sound track (write_avi)."""
+(csrc/mjpeg.hip; encode_jpeg_frames) in a RIFF AVI 1.0 container with an optional PCM sound track (write_avi).  gif_encoder="device" is a second,
+opt-in .gif writer: one palette for the clip (gif_palette, gif_lut), index map, LZW and sub-block packing on the device (csrc/gif.hip;
+encode_gif_frames) and the GIF89a container here (write_gif)."""
 import os
 import struct
 from pathlib import Path
@@ -176,7 +178,173 @@ def write_avi(path, jpeg_frames, width, height, fps, audio=None):
     return len(body) + 8
 
 
-def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90):
+# ---- GIF89a with one palette for the clip ----------------------------------------------------------------------------------------
+GIF_BINS = 32768                    # 5 bits per channel: bin = (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3)
+GIF_STRIP_ROWS = 16                 # image rows per LZW strip of encode_gif_frames: 768 workgroups for 24 frames of 512 rows
+GIF_SCRATCH_BYTES = 256 << 20       # encode_gif_frames holds at most this much index map, strip slots and packed frames per set of launches
+
+
+def _gif_hist(hist):
+    h = np.asarray(hist)
+    if h.shape != (GIF_BINS,) or h.dtype.kind not in "iu":
+        raise ValueError(f"expected an integer histogram of shape ({GIF_BINS},), got {h.dtype} {h.shape}")
+    h = h.astype(np.int64)
+    if (h < 0).any():
+        raise ValueError("histogram counts must not be negative")
+    return h
+
+
+def gif_palette(hist) -> np.ndarray:
+    """(32768,) pixel counts per bin -> (256, 3) uint8 palette by median cut over the occupied bins, in integer arithmetic only (the same table on
+    every call and every host).  A bin has the coordinates (r, g, b) = (bin >> 10, bin >> 5 & 31, bin & 31) and the centre 8 i + 4 per channel.
+
+    Up to 256 occupied bins: entry k is the centre of the k-th occupied bin in ascending bin order, the rest is zero.  Otherwise box 0 holds every
+    occupied bin and, until there are 256 boxes: a box's side along an axis is max - min + 1 of its bins' coordinates; among the boxes of two or more
+    bins the one with the largest (pixel count x longest side) is split, the lowest box index winning a tie; the axis is the longest side, R before G
+    before B on a tie; with c(v) the box's pixels at coordinate v of that axis and T their sum, the cut m is the smallest v with
+    2 (c(min) + ... + c(v)) >= T, lowered to max - 1 if it is max; bins with coordinate <= m keep the box's index, the others become the box with the
+    next free index.  Entry k is, per channel, the count-weighted mean of the centres of box k's bins, rounded half up:
+    floor((2 sum(c (8 i + 4)) + sum c) / (2 sum c))."""
+    h = _gif_hist(hist)
+    occ = np.flatnonzero(h)
+    pal = np.zeros((256, 3), np.uint8)
+    if occ.size == 0:
+        raise ValueError("gif_palette: the histogram is empty")
+    coord = np.stack([occ >> 10, (occ >> 5) & 31, occ & 31], axis=1).astype(np.int64)       # (bins, 3)
+    cnt = h[occ]
+    if occ.size <= 256:
+        pal[:occ.size] = 8 * coord + 4
+        return pal
+
+    def score(members):                                                                       # (count x longest side, axis), or None: not splittable
+        if members.size < 2:
+            return None
+        c = coord[members]
+        side = c.max(0) - c.min(0) + 1
+        axis = int(np.argmax(side))                                                           # first maximum: R, G, B
+        return int(cnt[members].sum()) * int(side[axis]), axis
+
+    boxes = [np.arange(occ.size)]
+    scores = [score(boxes[0])]
+    while len(boxes) < 256:
+        best = max((k for k in range(len(boxes)) if scores[k] is not None), key=lambda k: (scores[k][0], -k))
+        members, axis = boxes[best], scores[best][1]
+        v = coord[members, axis]
+        lo, hi = int(v.min()), int(v.max())
+        per = np.zeros(hi - lo + 1, np.int64)
+        np.add.at(per, v - lo, cnt[members])                                                  # int64 sums (bincount's weights are floats)
+        cum = np.cumsum(per)
+        m = lo + int(np.argmax(2 * cum >= cum[-1]))
+        m = min(m, hi - 1)
+        lower, upper = members[v <= m], members[v > m]
+        boxes[best] = lower
+        scores[best] = score(lower)
+        boxes.append(upper)
+        scores.append(score(upper))
+    for k, members in enumerate(boxes):
+        c = cnt[members]
+        tot = int(c.sum())
+        for ch in range(3):
+            pal[k, ch] = (2 * int((c * (8 * coord[members, ch] + 4)).sum()) + tot) // (2 * tot)
+    return pal
+
+
+def _gif_check_palette(palette):
+    pal = np.asarray(palette)
+    if pal.shape != (256, 3) or pal.dtype != np.uint8:
+        raise ValueError(f"palette must be uint8 (256, 3), got {pal.dtype} {pal.shape}")
+    return pal
+
+
+def gif_lut(palette) -> np.ndarray:
+    """(256, 3) uint8 palette -> (32768,) uint8: for every bin the palette entry nearest to the bin's centre (8 r + 4, 8 g + 4, 8 b + 4) by squared
+    RGB distance, the lowest index on a tie."""
+    pal = _gif_check_palette(palette).astype(np.int32)
+    centre = 8 * np.arange(32, dtype=np.int32) + 4
+    d = [(centre[:, None] - pal[None, :, ch]) ** 2 for ch in range(3)]                       # (32, 256) each
+    dist = d[0][:, None, None, :] + d[1][None, :, None, :] + d[2][None, None, :, :]          # (32, 32, 32, 256)
+    return np.argmin(dist.reshape(GIF_BINS, 256), axis=1).astype(np.uint8)                   # argmin returns the first minimum
+
+
+def encode_gif_frames(frames_u8, palette=None, strip_rows=None):
+    """(n, H, W, 3) uint8 RGB frames (a CUDA tensor, or host data that is uploaded) -> (palette (256, 3) uint8, n byte strings): each string is
+    one frame's GIF image data as write_gif takes it, LZW-coded against `palette` and cut into data sub-blocks with the 0x00 terminator.  Colour
+    histogram, index map (nearest palette entry of the pixel's 5-bit bin, no dithering), LZW and packing run on the device (csrc/gif.hip); the host
+    builds palette and lookup table from the 128 KB histogram (gif_palette / gif_lut, skipped for the histogram if `palette` is given) and receives
+    the sizes and ONE buffer of finished bytes per set of launches.  The bytes are the same on every call."""
+    from . import hip
+    x = torch.as_tensor(frames_u8)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"encode_gif_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
+    n, H, W, _ = x.shape
+    if n == 0 or H == 0 or W == 0:
+        raise ValueError(f"encode_gif_frames: empty clip {tuple(x.shape)}")
+    if H > 65535 or W > 65535:
+        raise ValueError(f"encode_gif_frames: a GIF frame is at most 65535 x 65535, got {W} x {H}")
+    if palette is not None:
+        palette = _gif_check_palette(palette).copy()
+    strip_rows = int(GIF_STRIP_ROWS if strip_rows is None else strip_rows)
+    if strip_rows < 1:
+        raise ValueError(f"encode_gif_frames: strip_rows must be at least 1, got {strip_rows}")
+    strip_rows = min(strip_rows, H)
+    if not x.is_cuda:
+        x = x.cuda()
+    x = x.contiguous()
+    if palette is None:
+        palette = gif_palette(hip.gif_histogram(x).cpu().numpy().view(np.uint32))
+    lut = torch.from_numpy(gif_lut(palette)).to(x.device)
+    strips = -(-H // strip_rows)
+    stride = hip.gif_strip_stride(W, strip_rows)
+    per_frame = H * W + strips * stride + hip.gif_packed_stride(strips, stride)
+    per_call = max(1, GIF_SCRATCH_BYTES // per_frame)
+    blobs = []
+    for f0 in range(0, n, per_call):
+        packed, sizes = hip.gif_pack(*hip.gif_lzw(hip.gif_index(x[f0:f0 + per_call], lut), strip_rows))
+        sizes = sizes.tolist()
+        if min(sizes) < 1:
+            raise RuntimeError("encode_gif_frames: the packed frame did not fit its slot (mmgt_gif_pack)")
+        data = packed[:, :max(sizes)].cpu().numpy()
+        blobs += [data[k, :sizes[k]].tobytes() for k in range(len(sizes))]
+    return palette, blobs
+
+
+def write_gif(path, palette, frame_blobs, W, H, fps, loop=0):
+    """GIF89a: header, logical screen descriptor with a 256-entry global colour table, the NETSCAPE2.0 loop extension (`loop` repetitions, 0 = for
+    ever), per frame a graphic control extension (delay, no disposal, no transparency) and an image descriptor covering the screen with no local
+    table, the LZW minimum code size 8 and the frame's data sub-blocks as encode_gif_frames returns them; then the trailer.  Returns the bytes
+    written.  A GIF delay is a whole number of centiseconds, round(100 / fps): 25 fps is 4 cs exactly, but most rates are not expressible
+    (8 fps -> 12 cs = 8.33 fps, 30 fps -> 3 cs = 33.3 fps).  DESIGN.md 4d lists the fields."""
+    pal = _gif_check_palette(palette)
+    blobs = [bytes(b) for b in frame_blobs]
+    if not blobs:
+        raise ValueError("write_gif: no frames")
+    if not (1 <= int(W) <= 65535 and 1 <= int(H) <= 65535):
+        raise ValueError(f"write_gif: a GIF screen is 1 .. 65535 pixels a side, got {W} x {H}")
+    if not float(fps) > 0:
+        raise ValueError(f"write_gif: fps must be positive, got {fps}")
+    delay = min(65535, int(round(100.0 / float(fps))))
+    loop = int(loop)
+    if not 0 <= loop <= 65535:
+        raise ValueError(f"write_gif: loop must be 0 .. 65535, got {loop}")
+    out = [b"GIF89a", struct.pack("<HHBBB", int(W), int(H), 0xF7, 0, 0), pal.tobytes(),
+           b"\x21\xff\x0bNETSCAPE2.0\x03\x01" + struct.pack("<H", loop) + b"\x00"]
+    gce = b"\x21\xf9\x04" + struct.pack("<BHB", 0, delay, 0) + b"\x00"
+    desc = b"\x2c" + struct.pack("<HHHHB", 0, 0, int(W), int(H), 0) + b"\x08"
+    for b in blobs:
+        if not b or b[-1] != 0:
+            raise ValueError("write_gif: a frame's data must be sub-blocks ending with the 0x00 terminator")
+        out += [gce, desc, b]
+    out.append(b"\x3b")
+    body = b"".join(out)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(body)
+    return len(body)
+
+
+def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90, gif_encoder="pil"):
+    if gif_encoder not in ("pil", "device"):
+        raise ValueError(f"gif_encoder must be 'pil' or 'device', got {gif_encoder!r}")
     if rescale:
         if torch.as_tensor(videos).dtype == torch.uint8:
             raise ValueError("rescale=True maps [-1, 1] floats to [0, 1]; uint8 frames are already in their final range")
@@ -187,7 +355,10 @@ def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=
     frames = frames_uint8(videos, n_rows)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     fmt = Path(path).suffix
-    if fmt == ".gif":
+    if fmt == ".gif" and gif_encoder == "device":
+        palette, blobs = encode_gif_frames(frames)
+        write_gif(path, palette, blobs, frames.shape[2], frames.shape[1], fps)
+    elif fmt == ".gif":
         from PIL import Image
         pil = [Image.fromarray(f) for f in frames]
         pil[0].save(fp=path, format="GIF", append_images=pil[1:], save_all=True, duration=(1 / fps * 1000), loop=0)

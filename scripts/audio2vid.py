@@ -60,6 +60,9 @@ def parse_args():
     p.add_argument("--format", default="npy", choices=["npy", "gif", "avi"],
                    help="avi = Motion-JPEG encoded on the device, with the samples of --audio_path as its PCM sound track")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
+    p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
+                   help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
+                        "on the device: mmgt_amd.video_out.encode_gif_frames)")
     p.add_argument("--wavlm", default="off", metavar="{off,random,PATH}",
                    help="WavLM-Large features of --audio_path as columns 0:1024 of the SMGA conditioning: off (hash-seeded stand-in, the default), "
                         "random (hash-seeded Large weights) or the path of a WavLM-Large.pt checkpoint")
@@ -250,7 +253,7 @@ def main():
         extra["bytes"] = write_avi(path, jpegs, a.W, a.H, fps, audio=sound)
         extra["encode_s"] = round(time.time() - t0, 3)
     else:
-        save_videos_grid(v, path, n_rows=1, fps=a.fps or 25)
+        save_videos_grid(v, path, n_rows=1, fps=a.fps or 25, gif_encoder=a.gif_encoder)
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
                       "dtype": a.dtype, "context_batch_size": a.context_batch_size, "keypoints_finite": bool(np.isfinite(kps).all()),
                       "mask_levels": [list(m.shape) for m in face], **timing, **extra}))

@@ -52,6 +52,9 @@ def parse_args():
     p.add_argument("--format", default="gif", choices=["gif", "npy", "avi"],
                    help="output container of the file-input mode; avi = Motion-JPEG encoded on the device (mmgt_amd.video_out)")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
+    p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
+                   help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
+                        "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -175,7 +178,7 @@ def run_files(a, dev, dtype):
         extra = {"bytes": write_avi(path, out.videos, a.W, a.H, a.fps), "quality": a.quality}
         shape = [1, len(out.videos), a.H, a.W, 3]
     else:
-        save_videos_grid(out.videos, path, n_rows=1, fps=a.fps)
+        save_videos_grid(out.videos, path, n_rows=1, fps=a.fps, gif_encoder=a.gif_encoder)
         shape = list(torch.as_tensor(out.videos).shape)
     print(json.dumps({"video": shape, "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype,
@@ -250,10 +253,16 @@ def main():
     os.makedirs(a.out_dir, exist_ok=True)
     path = os.path.join(a.out_dir, f"pose2vid_synth_{a.W}x{a.H}x{a.L}.pt")
     torch.save(v if torch.is_tensor(v) else torch.from_numpy(v), path)
+    extra = {}
+    if a.gif_encoder == "device" and a.format == "gif" and not a.no_decode:
+        from mmgt_amd.video_out import save_videos_grid
+        extra["gif"] = os.path.splitext(path)[0] + ".gif"
+        save_videos_grid(v, extra["gif"], n_rows=1, fps=a.fps, gif_encoder="device")
+        extra["gif_bytes"] = os.path.getsize(extra["gif"])
     print(json.dumps({"video": list(v.shape), "saved": path, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "windows_per_step": len(list(__import__("mmgt_amd.context", fromlist=["uniform"]).uniform(
                           0, a.steps, a.L, a.num_c, 1, 4))), "context_batch_size": a.context_batch_size, "dtype": a.dtype,
-                      "finite": bool(torch.as_tensor(v).isfinite().all())}))
+                      "finite": bool(torch.as_tensor(v).isfinite().all()), **extra}))
 
 
 if __name__ == "__main__":
