@@ -6,30 +6,24 @@ short sequences run the one-wave and 32-key forms of the generic kernel.
 
 fp32 mode: rtol 1e-3 / atol 1e-4; bf16: 2e-2 / 2e-2 (tests/test_hip_kernels.py `tol`).  Guards on every case: K and V sit in allocations
 with 64 NaN rows (columns, for V^T) behind the last key -- one key read past the end and the output is NaN --, and `out` is a view into a
-sentinel-filled buffer of which nothing outside the (batch, nq, heads * 64) block may change."""
+sentinel-filled buffer of which nothing outside the (batch, nq, heads * 64) block may change (the guards live in tests/attn_gate.py).
+
+The `peaked` tests run the row-major, cross-attention and packed-qkv shapes on Q = 8 x hash_uniform against the contract reference of
+tests/attn_gate.py: bf16 within 2 B = 2 u (sum P |v| + 2 |ref|) on every element, fp32 at rtol 1e-3 / atol 1e-4."""
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-from mmgt_amd.synthetic import hash_uniform  # noqa: E402
+from tests import attn_gate as G  # noqa: E402
+from tests.attn_gate import assert_rest_untouched, dev, in_wide, out_view, rnd, st, v_transposed  # noqa: E402, F401
 
 DT = [torch.float32, torch.bfloat16]
 HD = 64
-SENT = 7.0
-NAN = float("nan")
 
 
 def tol(dt):
     return dict(rtol=1e-3, atol=1e-4) if dt == torch.float32 else dict(rtol=2e-2, atol=2e-2)
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def rnd(name, shape, scale=1.0, dt=torch.float32):
-    return hash_uniform(name, shape, scale).to(dev()).to(dt)
 
 
 def _ref_attn(q, k, v, scale):
@@ -43,43 +37,6 @@ def ref_rows(q, k, v, heads):
     sp = lambda t: t.double().reshape(t.shape[0], t.shape[1], heads, HD).permute(0, 2, 1, 3)
     o = _ref_attn(sp(q), sp(k), sp(v), HD ** -0.5)
     return o.permute(0, 2, 1, 3).reshape(q.shape[0], q.shape[1], heads * HD)
-
-
-def in_wide(name, B, n, cols, dt, ld=None, col0=0, extra_rows=64, scale=1.0):
-    """A (B, n, cols) operand as a view into a NaN-filled (B, n + extra_rows, ld) allocation at column col0: the rows behind the last
-    token and the neighbouring columns are NaN."""
-    ld = cols if ld is None else ld
-    buf = torch.full((B, n + extra_rows, ld), NAN, device=dev(), dtype=dt)
-    view = buf[:, :n, col0:col0 + cols]
-    view.copy_(rnd(name, (B, n, cols), scale, dt))
-    return view
-
-
-def v_transposed(v, pad_cols=64):
-    """(B, nk, inner) -> V^T (B, inner, nk) as a view into rows of round_up(nk, 8) + pad_cols columns, NaN behind key nk"""
-    B, nk, inner = v.shape
-    buf = torch.full((B, inner, (nk + 7) // 8 * 8 + pad_cols), NAN, device=dev(), dtype=v.dtype)
-    buf[:, :, :nk] = v.transpose(1, 2)
-    return buf[:, :, :nk]
-
-
-def out_view(B, nq, cols, dt, ld=None, extra_rows=3):
-    """(buffer, view): the (B, nq, cols) output block inside a sentinel-filled (B + 1, nq + extra_rows, ld) buffer"""
-    ld = cols if ld is None else ld
-    buf = torch.full((B + 1, nq + extra_rows, ld), SENT, device=dev(), dtype=dt)
-    return buf, buf[:B, :nq, :cols]
-
-
-def assert_rest_untouched(buf, view):
-    """every element of `buf` outside `view` still holds the sentinel bit for bit (7.0 has one encoding)"""
-    chk = buf.clone()
-    chk[:view.shape[0], :view.shape[1], :view.shape[2]] = SENT
-    bits = torch.int32 if buf.dtype == torch.float32 else torch.int16
-    assert torch.equal(chk.view(bits), torch.full_like(chk, SENT).view(bits)), "the kernel wrote outside its output block"
-
-
-def st(t):
-    return (t.stride(0), 0, t.stride(1))
 
 
 def attn(q, k, v, o, heads, nq, nk, **kw):
@@ -110,6 +67,50 @@ def test_self_attention_row_major_v(dt, n):
     buf, o = out_view(B, n, inner, dt)
     attn(q, k, v, o, heads, n, n)
     check(o, ref_rows(q, k, v, heads), dt, f"self n={n} {dt}")
+    assert_rest_untouched(buf, o)
+
+
+@pytest.mark.parametrize("dt", DT)
+@pytest.mark.parametrize("n", [17, 80, 257])
+def test_self_attention_row_major_v_peaked(dt, n):
+    """test_self_attention_row_major_v's one-wave, ragged four-wave and 128 + 1 query shapes on peaked operands at the derived gate"""
+    B, heads = 2 + n % 2, 4 + n % 5
+    c = G.build("h64", HD, heads, B, n, n, 0, None, dt, G.PEAKED, dev(), guarded=True)
+    buf, o = out_view(B, n, heads * HD, dt)
+    attn(c.q, c.k, c.v, o, heads, n, n)
+    c.check(o)
+    assert_rest_untouched(buf, o)
+
+
+@pytest.mark.parametrize("dt", DT)
+def test_cross_attention_peaked(dt):
+    """(80, 82) of test_cross_attention_unequal_lengths_and_strides, its three token strides and NaN neighbour columns, on peaked operands"""
+    B, heads, nq, nk = 3, 8, 80, 82
+    d = heads * HD
+    q = in_wide("h64x.q", B, nq, d, dt, ld=2 * d, col0=0, extra_rows=0, scale=G.PEAKED)
+    k = in_wide("h64x.k", B, nk, d, dt, ld=3 * d, col0=d)
+    v = in_wide("h64x.v", B, nk, d, dt, ld=d + 8)
+    c = G.Case(f"cross (80, 82) peaked {dt}", q, k, v, heads, HD)
+    buf, o = out_view(B, nq, d, dt)
+    attn(q, k, v, o, heads, nq, nk)
+    c.check(o)
+    assert_rest_untouched(buf, o)
+
+
+@pytest.mark.parametrize("dt", DT)
+def test_packed_qkv_peaked(dt):
+    """test_packed_qkv_at_the_wav2vec_layout with the q columns of the packed tensor drawn at 8 x"""
+    heads, S = 12, 149
+    H = heads * HD
+    qkv = in_wide("w2vp.qkv", 1, S, 3 * H, dt)
+    qkv[..., :H] = rnd("w2vp.q", (1, S, H), G.PEAKED, dt)
+    q, k, v = qkv[..., :H], qkv[..., H:2 * H], qkv[..., 2 * H:]
+    c = G.Case(f"packed qkv peaked {dt}", q, k, v, heads, HD)
+    buf, o = out_view(1, S, H, dt)
+    from mmgt_amd import hip
+    hip.attention(q, k, v, o, batch=1, heads=heads, hd=HD, nq=S, nk=S, scale=HD ** -0.5, q_str=(S * 3 * H, 0, 3 * H), k_str=(S * 3 * H, 0, 3 * H),
+                  v_str=(S * 3 * H, 0, 3 * H), o_str=st(o))
+    c.check(o)
     assert_rest_untouched(buf, o)
 
 
