@@ -403,6 +403,25 @@ int mmgt_jpeg_compact(const unsigned char* segs, long seg_stride, const int* siz
                       int nseg, int mcu_rows, void* stream);
 /* Host: the luminance and chrominance quantiser tables of `quality` in zigzag order (the body of two DQT segments), 128 bytes. */
 int mmgt_jpeg_qtables(int quality, unsigned char* zigzag128);
+/* ---- JPEG input path (csrc/jpegdec.hip, csrc/jpegdec_core.h, mmgt_amd/video_in.py): baseline JPEG (SOF0, 8 bit, one interleaved scan)
+ * of a batch of n equally sized frames -> device-resident RGB.  ncomp is 1 (hs = vs = 1) or 3 with luma sampling hs x vs = 1x1, 2x1 or 2x2 and
+ * chroma 1x1; mcu_rows / mcu_cols = ceil(H / 8 vs), ceil(W / 8 hs).  Component c's plane has mcu_rows * v_c x mcu_cols * h_c blocks; a frame's
+ * planes follow each other, frame_blocks blocks in all.  tables: table_ints int32 words per frame in the layout csrc/jpegdec_core.h states (table
+ * selectors, four quantiser tables in natural order, MINCODE / MAXCODE / VALPTR / HUFFVAL of DC 0, DC 1, AC 0, AC 1).  Every buffer but sizes'
+ * outputs is a device pointer. */
+int mmgt_jpegdec_sizes(int H, int W, int ncomp, int hs, int vs, long long* frame_blocks, int* table_ints);
+/* Restart segment s = data[offsets[s], offsets[s + 1]) (markers removed, 0xFF 0x00 stuffing still in) holds the MCUs [seginfo[3 s + 1],
+ * seginfo[3 s + 2]) of frame seginfo[3 s]: one lane decodes it into coef (n, frame_blocks, 64) int16, natural order, zero-filled here first.
+ * status[s] = 0, or 1 a code longer than 16 bits, 2 a coefficient index past 63, 3 a DC category above 11 / AC above 10, 4 an accumulated DC
+ * outside [-2048, 2047], 5 data exhausted before the last block, 6 a descriptor outside the batch (nothing read).  Nothing is written out of
+ * range whatever the bytes hold. */
+int mmgt_jpegdec_entropy(const unsigned char* data, long long data_bytes, const long long* offsets, const int* seginfo, const int* tables,
+                         short* coef, int* status, int n, int nseg, int H, int W, int ncomp, int hs, int vs, void* stream);
+/* Dequantise + libjpeg's jpeg_idct_islow, + 128, clamp -> planes (n, frame_blocks * 64) uint8: component c's plane at its MCU-padded size. */
+int mmgt_jpegdec_idct(const short* coef, const int* tables, unsigned char* planes, int n, int H, int W, int ncomp, int hs, int vs, void* stream);
+/* libjpeg's fancy chroma up-sampling (replication when the chroma plane is 1 or 2 samples wide) + YCbCr -> RGB, cropped -> out (n, H, W, 3)
+ * uint8; one component: Y in all three channels. */
+int mmgt_jpegdec_color(const unsigned char* planes, unsigned char* out, int n, int H, int W, int ncomp, int hs, int vs, void* stream);
 /* ---- GIF output path (csrc/gif.hip, mmgt_amd/video_out.py): GIF89a image data of device-resident frames with ONE palette for the clip.
  * A colour's bin is (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) (15 bits).  Every buffer is a device pointer; frames, idx, out are 4-byte aligned, lut
  * 16-byte aligned.  n, H, W >= 1, H, W <= 65535, n * H * W < 2^32.  Like every entry: 0 on success, else mmgt_last_error() has the text and

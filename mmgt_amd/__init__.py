@@ -13,4 +13,10 @@ def __getattr__(name):
     if name in ("WavLM", "WavLMConfig"):
         from . import wavlm
         return getattr(wavlm, name)
+    if name in ("parse_jpeg", "decode_jpeg_frames", "read_frames_device"):
+        from . import video_in
+        return getattr(video_in, name)
+    if name in ("pose_tensor_device", "motion_masks_device"):
+        from . import inputs
+        return getattr(inputs, name)
     raise AttributeError(f"module 'mmgt_amd' has no attribute {name!r}")

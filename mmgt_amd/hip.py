@@ -111,6 +111,11 @@ _SIGS = {
     "mmgt_jpeg_scan": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "mmgt_jpeg_compact": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
     "mmgt_jpeg_qtables": (c_int, [c_int, c_void_p]),
+    "mmgt_jpegdec_sizes": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(c_int)]),
+    "mmgt_jpegdec_entropy": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, c_void_p]),
+    "mmgt_jpegdec_idct": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_jpegdec_color": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_histogram": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_index": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_lzw": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p]),
@@ -1041,6 +1046,61 @@ def jpeg_compact(segs, sizes, mcu_rows):
     _check(lib().mmgt_jpeg_compact(_ptr(segs), segs.shape[1], _ptr(sizes), _ptr(offsets), _ptr(data), total, nseg, int(mcu_rows), _stream()),
            "mmgt_jpeg_compact")
     return data, host
+
+
+# ------------------------------------------------------------------------------------------------------------ JPEG input (csrc/jpegdec.hip)
+
+
+def jpegdec_sizes(H, W, ncomp, hs, vs):
+    """(blocks per frame over all component planes, int32 words of one frame's table block); the library refuses geometry it does not decode."""
+    fb, ti = ctypes.c_longlong(0), c_int(0)
+    _check(lib().mmgt_jpegdec_sizes(int(H), int(W), int(ncomp), int(hs), int(vs), ctypes.byref(fb), ctypes.byref(ti)), "mmgt_jpegdec_sizes")
+    return fb.value, ti.value
+
+
+def jpegdec_entropy(data, offsets, seginfo, tables, n, H, W, ncomp, hs, vs):
+    """Restart segments -> (coef (n, frame_blocks, 64) int16 in natural order, status (nseg,) int32): include/mmgt_hip.h states the operands."""
+    _dev(data, offsets, seginfo, tables)
+    fb, ti = jpegdec_sizes(H, W, ncomp, hs, vs)
+    nseg = seginfo.shape[0]
+    if (data.dtype != torch.uint8 or data.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape != (nseg + 1,) or seginfo.dtype != torch.int32
+            or seginfo.shape != (nseg, 3) or tables.dtype != torch.int32 or tables.shape != (n, ti)
+            or not all(t.is_contiguous() for t in (data, offsets, seginfo, tables))):
+        raise RuntimeError("jpegdec_entropy: expected data uint8 (bytes,), offsets int64 (nseg + 1,), seginfo int32 (nseg, 3), tables int32 "
+                           f"(n, {ti}), all contiguous")
+    coef = torch.empty((n, fb, 64), device=data.device, dtype=torch.int16)
+    status = torch.empty((nseg,), device=data.device, dtype=torch.int32)
+    _check(lib().mmgt_jpegdec_entropy(_ptr(data), data.numel(), _ptr(offsets), _ptr(seginfo), _ptr(tables), _ptr(coef), _ptr(status), n, nseg,
+                                      H, W, ncomp, hs, vs, _stream()), "mmgt_jpegdec_entropy")
+    return coef, status
+
+
+def jpegdec_idct(coef, tables, H, W, ncomp, hs, vs):
+    """Coefficients of jpegdec_entropy -> (n, frame_blocks * 64) uint8 component planes."""
+    _dev(coef, tables)
+    fb, ti = jpegdec_sizes(H, W, ncomp, hs, vs)
+    n = coef.shape[0]
+    if (coef.dtype != torch.int16 or coef.shape != (n, fb, 64) or tables.dtype != torch.int32 or tables.shape != (n, ti)
+            or not coef.is_contiguous() or not tables.is_contiguous()):
+        raise RuntimeError(f"jpegdec_idct: expected coef int16 (n, {fb}, 64) and tables int32 (n, {ti}), contiguous")
+    planes = torch.empty((n, fb * 64), device=coef.device, dtype=torch.uint8)
+    _check(lib().mmgt_jpegdec_idct(_ptr(coef), _ptr(tables), _ptr(planes), n, H, W, ncomp, hs, vs, _stream()), "mmgt_jpegdec_idct")
+    return planes
+
+
+def jpegdec_color(planes, H, W, ncomp, hs, vs, out=None):
+    """Component planes of jpegdec_idct -> (n, H, W, 3) uint8 RGB (`out` to write into)."""
+    _dev(planes)
+    fb, _ = jpegdec_sizes(H, W, ncomp, hs, vs)
+    n = planes.shape[0]
+    if planes.dtype != torch.uint8 or planes.shape != (n, fb * 64) or not planes.is_contiguous():
+        raise RuntimeError(f"jpegdec_color: expected planes uint8 (n, {fb * 64}), contiguous")
+    if out is None:
+        out = torch.empty((n, H, W, 3), device=planes.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or out.shape != (n, H, W, 3) or not out.is_contiguous() or out.device != planes.device:
+        raise RuntimeError(f"jpegdec_color: out must be contiguous uint8 ({n}, {H}, {W}, 3) on {planes.device}")
+    _check(lib().mmgt_jpegdec_color(_ptr(planes), _ptr(out), n, H, W, ncomp, hs, vs, _stream()), "mmgt_jpegdec_color")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------------------ GIF (csrc/gif.hip)

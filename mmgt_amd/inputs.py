@@ -10,6 +10,9 @@ device (mmgt_amd/conditioning.py) instead of cv2 / PIL on the host.
                      (scripts/pose2vid.py:231-236)
   motion_masks       face / lips / hands mask frames -> blur_mask (resize 64 x 64, Gaussian 31 / 21 / 21, min-max normalise) ->
                      the 64 / 32 / 16 / 8 pyramid -> full = clamp(1 - face + lips + hands, 0, 1) per level (:239-271)
+  pose_tensor_device / motion_masks_device
+                     the same two from uint8 RGB frames that are already on the device (mmgt_amd.video_in.read_frames_device: Motion-JPEG
+                     decoded there): no PIL, no host copy of a frame
   load_checkpoint    a state dict from .safetensors / .pth / .pt / .bin / .ckpt or a diffusers-style directory
   split_net_checkpoint   the reference's `Net` checkpoint (net-<num_c>.pth, scripts/pose2vid.py:41-67,186-190) -> per-module dicts
 """
@@ -129,6 +132,37 @@ def motion_masks(face_frames: Sequence, lips_frames: Sequence, hands_frames: Opt
         hands = pyramid(hands_frames, 21)
     else:
         hands = [torch.zeros_like(m) for m in lips]                   # `Image.new("L", (64, 64), 0)` (:252)
+    return C.full_mask_with_hands(face, lips, hands), face, lips
+
+
+def pose_tensor_device(frames_u8: torch.Tensor, width: int, height: int) -> torch.Tensor:
+    """(L, H, W, 3) uint8 RGB on the device -> (1, 3, L, H, W) float32 in [0, 1] there: pose_tensor's u8 / 255 in fp32, exactly.  The frames must
+    already have the requested size: the antialiased resize of pose_tensor is a host (PIL) operation."""
+    x = frames_u8
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"pose_tensor_device: expected uint8 (L, H, W, 3) frames, got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    if tuple(x.shape[1:3]) != (height, width):
+        raise ValueError(f"pose_tensor_device: the frames are {x.shape[2]} x {x.shape[1]}, the sampler wants {width} x {height}; the antialiased resize "
+                         "is not done on the device: use read_frames + pose_tensor")
+    # the 256 quotients come from the host, where pose_tensor divides: a device division by a scalar multiplies by the rounded reciprocal instead
+    lut = (torch.arange(256, dtype=torch.float32) / 255.0).to(x.device)
+    idx = x.permute(3, 0, 1, 2).reshape(-1).to(torch.int32)
+    return torch.index_select(lut, 0, idx).view(1, 3, x.shape[0], height, width)
+
+
+def motion_masks_device(face_u8: torch.Tensor, lips_u8: torch.Tensor, hands_u8: Optional[torch.Tensor], length: int, img_size: int = 512):
+    """motion_masks for (L, h, w, 3) uint8 RGB mask frames that are already on the device: channel 0 is the mask (as in _mask_stack), and blur and
+    pyramid run where the frames are.  -> (full, face, lips) as motion_masks returns them."""
+    from . import conditioning as C
+
+    def pyramid(frames, ksize, name):
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 4 or not frames.is_cuda:
+            raise ValueError(f"motion_masks_device: {name} must be uint8 (L, h, w, 3) frames on the device")
+        u8 = frames[:length, :, :, 0].contiguous()
+        return [m.cpu() for m in C.mask_pyramid_device(C.blur_mask_device(u8, ksize), img_size)]
+    face = pyramid(face_u8, 31, "face")
+    lips = pyramid(lips_u8, 21, "lips")
+    hands = pyramid(hands_u8, 21, "hands") if hands_u8 is not None else [torch.zeros_like(m) for m in lips]
     return C.full_mask_with_hands(face, lips, hands), face, lips
 
 

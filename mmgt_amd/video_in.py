@@ -1,0 +1,322 @@
+"""Input path of the sampler from Motion-JPEG / JPEG files with the decode on the device: the counterpart of video_out's .avi writer.
+
+  parse_jpeg           the markers of one baseline JPEG file -> JpegHeader (geometry, tables, the restart segments' byte ranges); refuses on the
+                       host, with a ValueError naming the feature, everything the kernels do not decode
+  decode_jpeg_frames   a batch of equally sized JPEG files -> (n, H, W, 3) uint8 RGB on the device: Huffman decode, dequantiser + inverse DCT,
+                       chroma up-sampling and colour conversion run in csrc/jpegdec.hip, bit for bit libjpeg's (libjpeg-turbo's) default decode
+  read_frames_device   a Motion-JPEG .avi or a directory of .jpg frames -> the same tensor; anything else raises (inputs.read_frames is the host route)
+"""
+from dataclasses import dataclass, field
+from pathlib import Path
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+
+from .video_out import _AC_BITS, _AC_VALS, _DC_BITS
+
+# T.81 figure A.6: zigzag position -> natural index
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
+                   57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+# the tables a file without any DHT segment means (T.81 Annex K.3; the usual Motion-JPEG frame): (class, id) -> (BITS, HUFFVAL)
+ANNEX_K = {(0, 0): (_DC_BITS[0], bytes(range(12))), (0, 1): (_DC_BITS[1], bytes(range(12))),
+           (1, 0): (_AC_BITS[0], _AC_VALS[0]), (1, 1): (_AC_BITS[1], _AC_VALS[1])}
+
+_SOF_NAMES = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential", 0xC6: "differential progressive",
+              0xC7: "differential lossless", 0xC9: "arithmetic", 0xCA: "arithmetic progressive", 0xCB: "arithmetic lossless",
+              0xCD: "arithmetic differential sequential", 0xCE: "arithmetic differential progressive", 0xCF: "arithmetic differential lossless"}
+
+STATUS_TEXT = {1: "a Huffman code longer than 16 bits", 2: "a coefficient index past 63", 3: "a DC category above 11 or an AC category above 10",
+               4: "an accumulated DC outside [-2048, 2047]", 5: "data exhausted before the last block", 6: "a segment descriptor outside the batch"}
+
+# layout of a frame's table block: csrc/jpegdec_core.h (checked against the library's table_ints on every call)
+_TAB_Q, _HUFF_INTS = 16, 51 + 256
+_TAB_HUFF = _TAB_Q + 4 * 64
+TAB_INTS = _TAB_HUFF + 4 * _HUFF_INTS
+
+
+@dataclass
+class JpegHeader:
+    width: int
+    height: int
+    ncomp: int                                   # 1 or 3
+    hs: int                                      # luma sampling (chroma is 1 x 1); 1, 1 for one component: its scan is not interleaved
+    vs: int
+    tq: Tuple[int, ...]                          # per component: quantiser table, DC table, AC table
+    td: Tuple[int, ...]
+    ta: Tuple[int, ...]
+    qtables: Dict[int, np.ndarray]               # id -> (64,) in natural order
+    huffman: Dict[Tuple[int, int], Tuple[bytes, bytes]]      # (class 0 DC / 1 AC, id) -> (BITS, HUFFVAL); Annex K when the file has no DHT
+    restart_interval: int                        # MCUs per restart interval, 0 = none
+    scan_offset: int                             # first byte of the entropy-coded data
+    segments: List[Tuple[int, int]] = field(default_factory=list)       # [start, end) of every restart segment, markers excluded
+
+    @property
+    def mcu_rows(self):
+        return -(-self.height // (8 * self.vs))
+
+    @property
+    def mcu_cols(self):
+        return -(-self.width // (8 * self.hs))
+
+    @property
+    def mcus(self):
+        return self.mcu_rows * self.mcu_cols
+
+    @property
+    def geometry(self):
+        return self.height, self.width, self.ncomp, self.hs, self.vs
+
+
+def _check_huffman(bits, vals, what):
+    total, code = 0, 0
+    for length, n in enumerate(bits, 1):                                  # T.81 Annex C: the codes of each length must fit that length
+        code += n
+        if code > 1 << length:
+            raise ValueError(f"parse_jpeg: {what} has more codes of length {length} than that length holds")
+        code <<= 1
+        total += n
+    if total != len(vals) or total > 256:
+        raise ValueError(f"parse_jpeg: {what} counts {total} codes for {len(vals)} values")
+
+
+def parse_jpeg(data) -> JpegHeader:
+    """One baseline JPEG file (bytes; trailing bytes after EOI are ignored) -> JpegHeader.  ValueError for everything outside the decoder's scope."""
+    data = bytes(data)
+    if len(data) < 4 or data[:2] != b"\xff\xd8":
+        raise ValueError("parse_jpeg: not a JPEG file (missing SOI)")
+    pos, n = 2, len(data)
+    qtables, huffman, sof, sos, ri, adobe = {}, {}, None, None, 0, None
+    while sos is None:
+        if pos + 2 > n:
+            raise ValueError("parse_jpeg: missing SOS (the file ends in its headers)" if sof else "parse_jpeg: missing SOF (the file ends in its headers)")
+        if data[pos] != 0xFF:
+            raise ValueError(f"parse_jpeg: expected a marker at byte {pos}")
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        if pos >= n:
+            continue
+        m = data[pos]
+        pos += 1
+        if m == 0xD9:
+            raise ValueError("parse_jpeg: missing SOS (EOI before any scan)" if sof else "parse_jpeg: missing SOF (EOI before any frame header)")
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if pos + 2 > n:
+            continue
+        length = int.from_bytes(data[pos:pos + 2], "big")
+        body = data[pos + 2:pos + length]
+        if length < 2 or pos + length > n:
+            raise ValueError(f"parse_jpeg: segment {m:#04x} at byte {pos - 2} runs past the end of the file")
+        pos += length
+        if m == 0xDB:
+            k = 0
+            while k < len(body):
+                pq, tid = body[k] >> 4, body[k] & 15
+                if pq != 0:
+                    raise ValueError("parse_jpeg: 16-bit quantiser tables are not decoded (8-bit DQT only)")
+                if tid > 3 or k + 65 > len(body):
+                    raise ValueError("parse_jpeg: bad DQT segment")
+                q = np.zeros(64, np.int32)
+                q[ZIGZAG] = np.frombuffer(body[k + 1:k + 65], np.uint8)
+                qtables[tid] = q
+                k += 65
+        elif m == 0xC0:
+            if sof is not None:
+                raise ValueError("parse_jpeg: more than one SOF")
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise ValueError("parse_jpeg: bad SOF0 segment")
+            sof = body
+        elif m in _SOF_NAMES:
+            raise ValueError(f"parse_jpeg: {_SOF_NAMES[m]} JPEG (SOF{m - 0xC0}) is not decoded (baseline SOF0 only)")
+        elif m == 0xC4:
+            k = 0
+            while k < len(body):
+                tc, th = body[k] >> 4, body[k] & 15
+                if tc > 1 or th > 1 or k + 17 > len(body):
+                    raise ValueError("parse_jpeg: bad DHT segment (baseline: classes 0 - 1, tables 0 - 1)")
+                bits = body[k + 1:k + 17]
+                cnt = sum(bits)
+                vals = body[k + 17:k + 17 + cnt]
+                _check_huffman(bits, vals, f"DHT table {tc}/{th}")
+                huffman[(tc, th)] = (bits, vals)
+                k += 17 + cnt
+        elif m == 0xDD:
+            if len(body) != 2:
+                raise ValueError("parse_jpeg: bad DRI segment")
+            ri = int.from_bytes(body, "big")
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xDA:
+            if sof is None:
+                raise ValueError("parse_jpeg: missing SOF (SOS before any frame header)")
+            sos = body
+        # APPn, COM and anything else with a length: skipped
+    precision, height, width, ncomp = sof[0], int.from_bytes(sof[1:3], "big"), int.from_bytes(sof[3:5], "big"), sof[5]
+    if precision != 8:
+        raise ValueError(f"parse_jpeg: {precision}-bit samples are not decoded (8-bit only)")
+    if ncomp == 4:
+        raise ValueError("parse_jpeg: four components (CMYK / YCCK) are not decoded")
+    if ncomp not in (1, 3):
+        raise ValueError(f"parse_jpeg: {ncomp} components are not decoded (one or three)")
+    if height < 1 or width < 1:
+        raise ValueError(f"parse_jpeg: frame size {width} x {height}")
+    if adobe == 0 and ncomp == 3:
+        raise ValueError("parse_jpeg: Adobe APP14 transform 0 (RGB stored without a colour transform) is not decoded")
+    ids = [sof[6 + 3 * c] for c in range(ncomp)]
+    samp = [(sof[7 + 3 * c] >> 4, sof[7 + 3 * c] & 15) for c in range(ncomp)]
+    tq = tuple(sof[8 + 3 * c] for c in range(ncomp))
+    if ncomp == 1:
+        hs, vs = 1, 1
+    else:
+        hs, vs = samp[0]
+        if samp[0] not in ((1, 1), (2, 1), (2, 2)) or samp[1] != (1, 1) or samp[2] != (1, 1):
+            raise ValueError(f"parse_jpeg: sampling factors {samp} are not decoded (luma 1x1, 2x1 or 2x2 with chroma 1x1)")
+    if len(sos) < 1 or sos[0] != ncomp or len(sos) != 4 + 2 * sos[0]:
+        raise ValueError("parse_jpeg: more than one scan (the scan does not interleave all components)")
+    if [sos[1 + 2 * c] for c in range(ncomp)] != ids:
+        raise ValueError("parse_jpeg: the scan's components are not the frame's in order")
+    if tuple(sos[1 + 2 * ncomp:]) != (0, 63, 0):
+        raise ValueError("parse_jpeg: the scan is not a full sequential one (Ss 0, Se 63, Ah / Al 0)")
+    td = tuple(sos[2 + 2 * c] >> 4 for c in range(ncomp))
+    ta = tuple(sos[2 + 2 * c] & 15 for c in range(ncomp))
+    if not huffman:
+        huffman = dict(ANNEX_K)
+    for c in range(ncomp):
+        if tq[c] not in qtables:
+            raise ValueError(f"parse_jpeg: component {c} names quantiser table {tq[c]}, which no DQT defines")
+        if (0, td[c]) not in huffman or (1, ta[c]) not in huffman:
+            raise ValueError(f"parse_jpeg: component {c} names Huffman tables DC {td[c]} / AC {ta[c]}, which no DHT defines")
+    h = JpegHeader(width, height, ncomp, hs, vs, tq, td, ta, qtables, huffman, ri, pos)
+
+    # restart segments: inside entropy-coded data an 0xFF is followed only by 0x00, a marker or fill 0xFFs
+    a = np.frombuffer(data, np.uint8, offset=pos)
+    at = np.flatnonzero((a[:-1] == 0xFF) & (a[1:] != 0) & (a[1:] != 0xFF)) if a.size > 1 else np.zeros(0, np.int64)
+    marks = a[at + 1]
+    eoi = np.flatnonzero(marks == 0xD9)
+    other = np.flatnonzero((marks < 0xD0) | (marks > 0xD9))
+    if other.size and (eoi.size == 0 or other[0] < eoi[0]):
+        m = int(marks[other[0]])
+        raise ValueError("parse_jpeg: more than one scan is not decoded" if m in (0xDA, 0xC4, 0xDB, 0xDD) else
+                         f"parse_jpeg: unexpected marker {m:#04x} inside the scan")
+    if eoi.size == 0:
+        raise ValueError("parse_jpeg: missing EOI (the scan is truncated)")
+    k = int(eoi[0])
+    if k and ri == 0:
+        raise ValueError("parse_jpeg: restart marker out of sequence (the file defines no restart interval)")
+    if not np.array_equal(marks[:k], 0xD0 + (np.arange(k) & 7)):
+        raise ValueError("parse_jpeg: restart marker out of sequence")
+    need = -(-h.mcus // ri) if ri else 1
+    if k + 1 != need:
+        raise ValueError(f"parse_jpeg: the scan has {k + 1} restart intervals, {'fewer' if k + 1 < need else 'more'} than the frame's "
+                         f"{h.mcus} MCUs need ({need})")
+    starts = np.concatenate([[0], at[:k] + 2]) + pos
+    ends = at[:k + 1] + pos
+    h.segments = list(zip(starts.tolist(), ends.tolist()))
+    return h
+
+
+def huffman_decode_arrays(bits, vals) -> np.ndarray:
+    """BITS / HUFFVAL -> the int32 block of one table: MINCODE[0..16], MAXCODE[0..16] (-1: none), VALPTR[0..16] (T.81 F.2.2.3), HUFFVAL[0..255]."""
+    out = np.zeros(_HUFF_INTS, np.int32)
+    out[17:34] = -1
+    code, k = 0, 0
+    for length in range(1, 17):
+        n = bits[length - 1]
+        if n:
+            out[length] = code
+            out[34 + length] = k
+            code += n
+            k += n
+            out[17 + length] = code - 1
+        code <<= 1
+    out[51:51 + len(vals)] = np.frombuffer(bytes(vals), np.uint8)
+    return out
+
+
+def frame_tables(h: JpegHeader) -> np.ndarray:
+    """One frame's table block for the kernels (csrc/jpegdec_core.h)."""
+    t = np.zeros(TAB_INTS, np.int32)
+    for c in range(h.ncomp):
+        t[c], t[3 + c], t[6 + c] = h.tq[c], h.td[c], h.ta[c]
+    for tid, q in h.qtables.items():
+        t[_TAB_Q + 64 * tid:_TAB_Q + 64 * tid + 64] = q
+    for (tc, th), (bits, vals) in h.huffman.items():
+        o = _TAB_HUFF + (2 * tc + th) * _HUFF_INTS
+        t[o:o + _HUFF_INTS] = huffman_decode_arrays(bits, vals)
+    return t
+
+
+def batch_operands(jpegs, headers=None):
+    """Host-side operands of one decode call: (headers, data uint8 (bytes,), offsets int64 (nseg + 1,), seginfo int32 (nseg, 3), tables int32
+    (n, TAB_INTS)).  Segment s is data[offsets[s]:offsets[s + 1]] and holds the MCUs [seginfo[s, 1], seginfo[s, 2]) of frame seginfo[s, 0]."""
+    jpegs = [bytes(j) for j in jpegs]
+    headers = [parse_jpeg(j) for j in jpegs] if headers is None else headers
+    if not headers:
+        raise ValueError("decode_jpeg_frames: no frames")
+    for k, h in enumerate(headers):
+        if h.geometry != headers[0].geometry:
+            raise ValueError(f"decode_jpeg_frames: frame {k} is {h.width} x {h.height}, {h.ncomp} components, luma sampling {h.hs}x{h.vs}; frame 0 is "
+                             f"{headers[0].width} x {headers[0].height}, {headers[0].ncomp}, {headers[0].hs}x{headers[0].vs}: one call decodes one size")
+    parts, sizes, info = [], [], []
+    for f, (j, h) in enumerate(zip(jpegs, headers)):
+        step = h.restart_interval or h.mcus
+        for s, (a, b) in enumerate(h.segments):
+            parts.append(j[a:b])
+            sizes.append(b - a)
+            info.append((f, s * step, min((s + 1) * step, h.mcus)))
+    data = np.frombuffer(b"".join(parts) or b"\0", np.uint8)
+    offsets = np.zeros(len(sizes) + 1, np.int64)
+    np.cumsum(sizes, out=offsets[1:])
+    return headers, data, offsets, np.asarray(info, np.int32).reshape(-1, 3), np.stack([frame_tables(h) for h in headers])
+
+
+def decode_jpeg_frames(jpegs, device="cuda", out=None):
+    """n baseline JPEG files of one size and sampling (quantiser and Huffman tables may differ per frame) -> (n, H, W, 3) uint8 RGB on `device`,
+    contiguous; a greyscale file gives Y in all three channels (what Image.convert("RGB") gives).  `out`: a tensor of that shape to write into.
+    Out-of-scope files raise ValueError before anything is launched; entropy-coded data that does not decode raises RuntimeError naming the
+    first bad frame and segment (the status words are read once per call), and no pixels are returned."""
+    import torch
+    from . import hip
+    headers, data, offsets, seginfo, tables = batch_operands(jpegs)
+    H, W, ncomp, hs, vs = headers[0].geometry
+    dev = torch.device(device)
+    fb, ti = hip.jpegdec_sizes(H, W, ncomp, hs, vs)
+    if ti != TAB_INTS:
+        raise RuntimeError(f"decode_jpeg_frames: the library's table block has {ti} words, this module builds {TAB_INTS}")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_data, d_tables = up(data.copy()), up(tables)
+    coef, status = hip.jpegdec_entropy(d_data, up(offsets), up(seginfo), d_tables, len(headers), H, W, ncomp, hs, vs)
+    planes = hip.jpegdec_idct(coef, d_tables, H, W, ncomp, hs, vs)
+    bad = torch.nonzero(status).flatten()[:1].cpu()                          # the one read of the status words (it also orders the launches)
+    if bad.numel():
+        s = int(bad[0])
+        code = int(status[s])
+        f = int(seginfo[s, 0])
+        raise RuntimeError(f"decode_jpeg_frames: frame {f}, restart segment {s - int(np.searchsorted(seginfo[:, 0], f))}: "
+                           f"{STATUS_TEXT.get(code, f'status {code}')}")
+    return hip.jpegdec_color(planes, H, W, ncomp, hs, vs, out=out)
+
+
+def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
+    """(L, H, W, 3) uint8 RGB frames of `path` on `device`, decoded there: a Motion-JPEG .avi (what video_out.write_avi writes, or any stock
+    tool's `-c:v mjpeg`) or a directory whose images are all .jpg / .jpeg (sorted by name).  Everything else raises: inputs.read_frames is the
+    host route, and the caller chooses it."""
+    from .inputs import IMAGE_SUFFIXES, mjpeg_avi_frames
+    p = Path(path)
+    if not p.exists():
+        raise FileNotFoundError(f"read_frames_device: {p} does not exist")
+    if p.is_dir():
+        files = sorted(f for f in p.iterdir() if f.is_file() and f.suffix.lower() in IMAGE_SUFFIXES)
+        other = [f.name for f in files if f.suffix.lower() not in (".jpg", ".jpeg")]
+        if not files or other:
+            raise RuntimeError(f"read_frames_device: {p} must hold .jpg / .jpeg frames only ({'found ' + other[0] if other else 'no images'}); "
+                               "use inputs.read_frames for other inputs")
+        jpegs = [f.read_bytes() for f in (files if limit is None else files[:limit])]
+    else:
+        jpegs = mjpeg_avi_frames(p, limit) if p.suffix.lower() == ".avi" else None
+        if jpegs is None:
+            raise RuntimeError(f"read_frames_device: {p.name} is neither a Motion-JPEG .avi nor a directory of .jpg frames; "
+                               "use inputs.read_frames for other inputs")
+    if not jpegs:
+        raise RuntimeError(f"read_frames_device: no frames in {p}")
+    return decode_jpeg_frames(jpegs, device)

@@ -11,7 +11,8 @@
 pose / mask / audio inputs, everything a pure function of names (mmgt_amd/synthetic.py); prints the timing breakdown.
 Without --synthetic the inputs are FILES, as in the reference (scripts/pose2vid.py:196-271): the reference image through PIL, the
 pose / mask clips as directories of images, .npy stacks or animated images (mmgt_amd/inputs.py: video containers need PyAV / cv2,
-which this build does not include, and say so), the masks blurred / resampled on the device (mmgt_amd/conditioning.py).  Weights
+which this build does not include, and say so), the masks blurred / resampled on the device (mmgt_amd/conditioning.py).  --decoder device
+reads Motion-JPEG .avi clips or directories of .jpg frames on the GPU instead (mmgt_amd/video_in.py).  Weights
 come from the checkpoints the config yaml names (:137-190) -- or, with --random-weights, from the hash-seeded initialisation (no
 checkpoint exists in this image).  The clip is written as .gif / .npy (mp4 muxing is out of scope: mmgt_amd/video_out.py).
 """
@@ -55,6 +56,9 @@ def parse_args():
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
                         "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
+    p.add_argument("--decoder", default="pil", choices=["pil", "device"],
+                   help="how --pose_path and the mask paths are read: pil = on the host (any input read_frames takes); device = Motion-JPEG "
+                        ".avi or a directory of .jpg frames, decoded on the GPU (mmgt_amd.video_in; frames must already be W x H)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -138,10 +142,37 @@ def build_from_checkpoints(cfg_path, num_c, dev, dtype):
                               scheduler=DDIMScheduler(**infer.get("noise_scheduler_kwargs", {})))
 
 
+def load_inputs(a, dev):
+    """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG on
+    the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
+    from mmgt_amd import inputs
+    device = getattr(a, "decoder", "pil") == "device"
+    if device:
+        from mmgt_amd.video_in import read_frames_device
+        read = lambda path: read_frames_device(path, a.L, dev)
+    else:
+        read = lambda path: inputs.read_frames(path, a.L)
+    pose_frames = read(a.pose_path)
+    face_frames = read(a.face_mask_path)
+    lips_frames = read(a.lips_mask_path)
+    hands_frames = read(a.hands_mask_path) if a.hands_mask_path and os.path.exists(a.hands_mask_path) else None
+    L = min(len(pose_frames), len(face_frames), len(lips_frames), len(hands_frames) if hands_frames is not None else 10 ** 9, a.L)
+    if L < 1:
+        raise SystemExit("pose2vid: no usable frames (check the pose / mask inputs)")
+    if L < a.L:
+        print(f"note: {L} usable frames < L = {a.L}: sampling {L} frames")
+    if device:
+        pose = inputs.pose_tensor_device(pose_frames[:L], a.W, a.H)           # stays on the device: the pipeline moves it there anyway
+        full, face, lips = inputs.motion_masks_device(face_frames, lips_frames, hands_frames, L, a.H)
+    else:
+        pose = inputs.pose_tensor(pose_frames[:L], a.W, a.H)
+        full, face, lips = inputs.motion_masks(face_frames, lips_frames, hands_frames, L, dev, a.H)
+    return pose, full, face, lips, L
+
+
 def run_files(a, dev, dtype):
     """The reference's single-sample mode on files (:196-300)."""
     from PIL import Image
-    from mmgt_amd import inputs
     from mmgt_amd.video_out import save_videos_grid
     for name in ("image_path", "pose_path", "face_mask_path", "lips_mask_path"):
         if not getattr(a, name):
@@ -150,17 +181,7 @@ def run_files(a, dev, dtype):
     pipe = build_synthetic(dev, dtype) if a.random_weights else build_from_checkpoints(a.config, a.num_c, dev, dtype)
     t_build = time.time() - t0
     ref_img = Image.open(a.image_path).convert("RGB")
-    pose_frames = inputs.read_frames(a.pose_path, a.L)
-    face_frames = inputs.read_frames(a.face_mask_path, a.L)
-    lips_frames = inputs.read_frames(a.lips_mask_path, a.L)
-    hands_frames = inputs.read_frames(a.hands_mask_path, a.L) if a.hands_mask_path and os.path.exists(a.hands_mask_path) else None
-    L = min(len(pose_frames), len(face_frames), len(lips_frames), len(hands_frames) if hands_frames else 10 ** 9, a.L)
-    if L < 1:
-        raise SystemExit("pose2vid: no usable frames (check the pose / mask inputs)")
-    if L < a.L:
-        print(f"note: {L} usable frames < L = {a.L}: sampling {L} frames")
-    pose = inputs.pose_tensor(pose_frames[:L], a.W, a.H)
-    full, face, lips = inputs.motion_masks(face_frames, lips_frames, hands_frames, L, dev, a.H)
+    pose, full, face, lips, L = load_inputs(a, dev)
     audio = torch.zeros(1, L, 32, 768)                        # pose2vid runs with null audio (:279)
     gen = torch.manual_seed(a.seed)
     torch.cuda.synchronize()
