@@ -422,6 +422,20 @@ int mmgt_jpegdec_idct(const short* coef, const int* tables, unsigned char* plane
 /* libjpeg's fancy chroma up-sampling (replication when the chroma plane is 1 or 2 samples wide) + YCbCr -> RGB, cropped -> out (n, H, W, 3)
  * uint8; one component: Y in all three channels. */
 int mmgt_jpegdec_color(const unsigned char* planes, unsigned char* out, int n, int H, int W, int ncomp, int hs, int vs, void* stream);
+/* ---- device image resize (csrc/resize.hip, csrc/resample_core.h): PIL's ImagingResample for 8-bit images, Image.resize with BILINEAR /
+ * BICUBIC / LANCZOS, bit for bit.  in (n, Hs, Ws, C) uint8 interleaved, C = 1 or 3, every side 1 .. 16384, upscale or downscale.  The caller hands
+ * in PIL's integer coefficient tables (mmgt_amd.conditioning.pil_resample_tables) per axis that changes: bounds[D][2] = (first tap, tap count) with
+ * 0 <= first and first + count <= S, kk[D][ksize] = weights with 22 fractional bits, count <= ksize, 255 * sum |kk| + 2^21 < 2^31 per row.  A
+ * horizontal launch runs if Wd != Ws, a vertical launch if Hd != Hs, each pass out = clip8((2^21 + sum u8 * k) >> 22) per band; when both run the
+ * uint8 intermediate (n, Hs, Wd, C) goes to `tmp` (mmgt_resize_u8_workspace bytes; may be null otherwise).  A pass whose size does not change is
+ * skipped.  The last launch -- or, when neither size changes, a copy launch -- writes exactly one of
+ *   out_u8   (n, Hd, Wd, C) uint8 interleaved, or
+ *   out_f32  (C, n, Hd, Wd) float planar, out = lut[c * 256 + value], lut = C x 256 floats from the caller (no device division).
+ * in, tmp and out are different buffers; the axis tables of an unchanged axis may be null.  Bad arguments return 1 before any launch. */
+int mmgt_resize_u8_workspace(int n, int Hs, int Ws, int Hd, int Wd, int C, long long* bytes);
+int mmgt_resize_u8(const unsigned char* in, unsigned char* tmp, unsigned char* out_u8, float* out_f32, const float* lut, int n, int Hs, int Ws,
+                   int Hd, int Wd, int C, const int* bounds_x, const int* kk_x, int ksize_x, const int* bounds_y, const int* kk_y, int ksize_y,
+                   void* stream);
 /* ---- GIF output path (csrc/gif.hip, mmgt_amd/video_out.py): GIF89a image data of device-resident frames with ONE palette for the clip.
  * A colour's bin is (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) (15 bits).  Every buffer is a device pointer; frames, idx, out are 4-byte aligned, lut
  * 16-byte aligned.  n, H, W >= 1, H, W <= 65535, n * H * W < 2^32.  Like every entry: 0 on success, else mmgt_last_error() has the text and

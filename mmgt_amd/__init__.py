@@ -16,7 +16,7 @@ def __getattr__(name):
     if name in ("parse_jpeg", "decode_jpeg_frames", "read_frames_device"):
         from . import video_in
         return getattr(video_in, name)
-    if name in ("pose_tensor_device", "motion_masks_device"):
+    if name in ("pose_tensor_device", "motion_masks_device", "resize_frames_device", "ref_image_tensors_device"):
         from . import inputs
         return getattr(inputs, name)
     raise AttributeError(f"module 'mmgt_amd' has no attribute {name!r}")

@@ -87,7 +87,88 @@ def pil_bilinear_tables(in_size: int, out_size: int):
     return torch.tensor(bounds, dtype=torch.int32), torch.tensor(kk, dtype=torch.int32)
 
 
+def _bicubic(x):
+    a = -0.5
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def _sinc(x):
+    if x == 0.0:
+        return 1.0
+    x = x * math.pi
+    return math.sin(x) / x
+
+
+RESAMPLE_FILTERS = {                                   # name -> (support, kernel), as Resample.c defines them
+    "bilinear": (1.0, lambda x: 1.0 - abs(x) if abs(x) < 1.0 else 0.0),
+    "bicubic": (2.0, _bicubic),
+    "lanczos": (3.0, lambda x: _sinc(x) * _sinc(x / 3) if -3.0 <= x < 3.0 else 0.0),
+}
+
+
+def pil_resample_tables(in_size: int, out_size: int, filter: str = "bilinear"):
+    """pil_bilinear_tables for any of Pillow's three convolution filters the reference reaches (BILINEAR: transforms.Resize; BICUBIC:
+    Image.resize's default; LANCZOS: VaeImageProcessor): precompute_coeffs + normalize_coeffs_8bpc, step by step in Python floats.
+    -> bounds (out, 2) int32 (first tap, tap count), kk (out, ksize) int32 with 22 fractional bits.  A row whose accumulator
+    255 * sum|k| + 2^21 could leave an int32 is refused (ValueError); so is a size outside 1 .. 16384."""
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError(f"pil_resample_tables: filter {filter!r} is not one of {sorted(RESAMPLE_FILTERS)}")
+    in_size, out_size = int(in_size), int(out_size)
+    if not (1 <= in_size <= 16384 and 1 <= out_size <= 16384):
+        raise ValueError(f"pil_resample_tables: sizes {in_size} -> {out_size} must lie in 1 .. 16384")
+    fsupport, f = RESAMPLE_FILTERS[filter]
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = fsupport * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    bounds, kk = [], []
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        w = [f((x + xmin - center + 0.5) * ss) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        if ww != 0.0:
+            w = [v / ww for v in w]
+        k = [int(0.5 + v * (1 << 22)) if v >= 0 else int(-0.5 + v * (1 << 22)) for v in w]
+        if 255 * sum(abs(v) for v in k) + (1 << 21) > 2 ** 31 - 1:
+            raise ValueError(f"pil_resample_tables: {filter} {in_size} -> {out_size}: the weights of output sample {xx} overflow a 32-bit accumulator")
+        bounds.append((xmin, xmax))
+        kk.append(k + [0] * (ksize - xmax))
+    return torch.tensor(bounds, dtype=torch.int32), torch.tensor(kk, dtype=torch.int32)
+
+
 _TABLES = {}
+_RESIZE_TABLES = {}
+
+
+def resample_tables_device(in_size: int, out_size: int, filter: str, device):
+    """pil_resample_tables on `device`, computed once per (in, out, filter, device); None when the size does not change (the pass is skipped)."""
+    if in_size == out_size:
+        return None
+    key = (int(in_size), int(out_size), filter, torch.device(device))
+    if key not in _RESIZE_TABLES:
+        b, k = pil_resample_tables(in_size, out_size, filter)
+        _RESIZE_TABLES[key] = (b.to(device), k.to(device))
+    return _RESIZE_TABLES[key]
+
+
+def resize_u8_device(frames_u8: torch.Tensor, height: int, width: int, filter: str = "bilinear", lut=None, out=None) -> torch.Tensor:
+    """(n, h, w, C) uint8 frames on the GPU, C = 1 or 3 -> PIL's Image.resize((width, height), filter) of each frame, bit for bit (csrc/resize.hip,
+    DESIGN 4f): (n, height, width, C) uint8, or with lut (C, 256) float32 the planar (C, n, height, width) float32 lut[c][value]."""
+    from . import hip
+    dev = frames_u8.device
+    return hip.resize_u8(frames_u8, height, width, resample_tables_device(frames_u8.shape[2], width, filter, dev),
+                         resample_tables_device(frames_u8.shape[1], height, filter, dev), lut=lut, out=out)
 
 
 def mask_pyramid_device(masks_u8: torch.Tensor, img_size: int = 512) -> List[torch.Tensor]:
@@ -125,16 +206,18 @@ def process_audio_emb_device(audio_emb: torch.Tensor) -> torch.Tensor:
 def pose_frames_device(kp_normalised: torch.Tensor, height: int = 512, width: int = 512):
     """kp_normalised (L, 402) fp32 on the GPU: SMGA's output after the seam smoothing (scripts/audio2vid.py:351-376) ->
     (pose (1, 3, L, height, width) fp32 in [0, 1] = ToTensor of the drawn frames after transforms.Resize((height, width)), :436-441;
-     face_u8, lips_u8, hands_u8 (L, 512, 512) uint8 mask frames for blur_mask_device).  The reference draws at 512 x 512; other square
-    sizes go through PIL's bilinear resampling per channel (what torchvision's Resize on a PIL image is), bit-exact with PIL."""
+     face_u8, lips_u8, hands_u8 (L, 512, 512) uint8 mask frames for blur_mask_device).  The reference draws at 512 x 512; other sizes
+    go through PIL's bilinear resampling (what torchvision's Resize on a PIL image is), bit-exact with PIL: square sizes up to 128 per channel
+    through mmgt_resample_u8, every other size through mmgt_resize_u8."""
     from . import hip
     kp = kp_normalised.to(torch.float32).reshape(kp_normalised.shape[0], 134, 3).contiguous()
     pose_u8, hands, lips, face = hip.dwpose_draw(kp)
     if (height, width) == (512, 512):
         pose = pose_u8.permute(3, 0, 1, 2)[None].to(torch.float32) / 255.0
     else:
-        if height != width:
-            raise NotImplementedError("pose_frames_device: square frames only (the reference's configs are 512 x 512)")
+        if height != width or 512 * height > 64 * 1024:        # beyond mmgt_resample_u8 (square, intermediate in LDS): the tiled resize, same bytes
+            lut = (torch.arange(256, dtype=torch.float32) / 255.0).repeat(3, 1).to(pose_u8.device)       # ToTensor's quotients, from the host
+            return resize_u8_device(pose_u8, height, width, "bilinear", lut=lut)[None], face, lips, hands
         key = (512, height, pose_u8.device)
         if key not in _TABLES:
             b, c = pil_bilinear_tables(512, height)

@@ -116,6 +116,9 @@ _SIGS = {
                                      c_int, c_int, c_int, c_void_p]),
     "mmgt_jpegdec_idct": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_jpegdec_color": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_resize_u8_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "mmgt_resize_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                               c_void_p, c_void_p, c_int, c_void_p]),
     "mmgt_gif_histogram": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_index": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_lzw": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p]),
@@ -949,6 +952,53 @@ def resample_u8(x, D, bounds, coeffs, as_float=True):
     out = torch.empty((x.shape[0], D, D), device=x.device, dtype=torch.float32 if as_float else torch.uint8)
     _check(lib().mmgt_resample_u8(_ptr(x), _ptr(out) if as_float else None, None if as_float else _ptr(out), x.shape[0], x.shape[1], D,
                                   _ptr(bounds), _ptr(coeffs), coeffs.shape[1], _stream()), "mmgt_resample_u8")
+    return out
+
+
+def resize_u8_workspace(n, Hs, Ws, Hd, Wd, C):
+    """Bytes of the uint8 intermediate a resize_u8 call of that shape needs (0 unless both sizes change)."""
+    b = ctypes.c_longlong(0)
+    _check(lib().mmgt_resize_u8_workspace(int(n), int(Hs), int(Ws), int(Hd), int(Wd), int(C), ctypes.byref(b)), "mmgt_resize_u8_workspace")
+    return b.value
+
+
+def resize_u8(x, Hd, Wd, tables_x=None, tables_y=None, lut=None, out=None, tmp=None):
+    """(n, Hs, Ws, C) uint8 frames, C = 1 or 3 -> PIL's Image.resize((Wd, Hd)) of every frame (see mmgt_resize_u8).  tables_x / tables_y are the
+    (bounds (D, 2), kk (D, ksize)) int32 device tensors of conditioning.pil_resample_tables for the axis that changes.  Without `lut` the result is
+    (n, Hd, Wd, C) uint8; with lut (C, 256) float32 it is (C, n, Hd, Wd) float32 = lut[c][value].  `out` / `tmp` (uint8, at least the workspace
+    size) to write into the caller's buffers."""
+    _dev(x, lut, out, tmp)
+    if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous():
+        raise RuntimeError(f"resize_u8: expected contiguous uint8 (n, H, W, C) frames, got {x.dtype} {tuple(x.shape)}")
+    n, Hs, Ws, C = x.shape
+    Hd, Wd = int(Hd), int(Wd)
+    ws = resize_u8_workspace(n, Hs, Ws, Hd, Wd, C)                   # checks the shape
+    args = []
+    for name, tabs, S, D in (("tables_x", tables_x, Ws, Wd), ("tables_y", tables_y, Hs, Hd)):
+        if S == D:
+            args += [None, None, 0]
+            continue
+        if tabs is None:
+            raise RuntimeError(f"resize_u8: {name} is needed ({S} -> {D})")
+        b, k = tabs
+        _dev(b, k)
+        if b.dtype != torch.int32 or k.dtype != torch.int32 or tuple(b.shape) != (D, 2) or k.dim() != 2 or k.shape[0] != D or \
+                not b.is_contiguous() or not k.is_contiguous():
+            raise RuntimeError(f"resize_u8: {name} must be contiguous int32 bounds ({D}, 2) and weights ({D}, ksize)")
+        args += [_ptr(b), _ptr(k), k.shape[1]]
+    if lut is not None and (lut.dtype != torch.float32 or tuple(lut.shape) != (C, 256) or not lut.is_contiguous()):
+        raise RuntimeError(f"resize_u8: lut must be contiguous float32 ({C}, 256)")
+    shape, dtype = ((n, Hd, Wd, C), torch.uint8) if lut is None else ((C, n, Hd, Wd), torch.float32)
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=dtype)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+        raise RuntimeError(f"resize_u8: out must be contiguous {dtype} {shape}")
+    if ws and tmp is None:
+        tmp = torch.empty((ws,), device=x.device, dtype=torch.uint8)
+    elif ws and (tmp.dtype != torch.uint8 or tmp.numel() < ws or not tmp.is_contiguous()):
+        raise RuntimeError(f"resize_u8: tmp must be contiguous uint8 of at least {ws} bytes")
+    _check(lib().mmgt_resize_u8(_ptr(x), _ptr(tmp) if ws else None, _ptr(out) if lut is None else None, None if lut is None else _ptr(out), _ptr(lut),
+                                n, Hs, Ws, Hd, Wd, C, *args, _stream()), "mmgt_resize_u8")
     return out
 
 

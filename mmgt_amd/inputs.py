@@ -12,7 +12,11 @@ device (mmgt_amd/conditioning.py) instead of cv2 / PIL on the host.
                      the 64 / 32 / 16 / 8 pyramid -> full = clamp(1 - face + lips + hands, 0, 1) per level (:239-271)
   pose_tensor_device / motion_masks_device
                      the same two from uint8 RGB frames that are already on the device (mmgt_amd.video_in.read_frames_device: Motion-JPEG
-                     decoded there): no PIL, no host copy of a frame
+                     decoded there): no PIL, no host copy of a frame.  pose_tensor_device(resize=True) takes frames of any size:
+                     PIL's antialiased bilinear resize runs on the device, byte for byte
+  resize_frames_device / ref_image_tensors_device
+                     PIL's Image.resize (bilinear / bicubic / Lanczos) on device frames, and the reference image's two prologue inputs
+                     (the VAE's Lanczos-resized [-1, 1] tensor, CLIP's bicubic 224 x 224 normalised pixel values) from a device image
   load_checkpoint    a state dict from .safetensors / .pth / .pt / .bin / .ckpt or a diffusers-style directory
   split_net_checkpoint   the reference's `Net` checkpoint (net-<num_c>.pth, scripts/pose2vid.py:41-67,186-190) -> per-module dicts
 """
@@ -135,19 +139,62 @@ def motion_masks(face_frames: Sequence, lips_frames: Sequence, hands_frames: Opt
     return C.full_mask_with_hands(face, lips, hands), face, lips
 
 
-def pose_tensor_device(frames_u8: torch.Tensor, width: int, height: int) -> torch.Tensor:
-    """(L, H, W, 3) uint8 RGB on the device -> (1, 3, L, H, W) float32 in [0, 1] there: pose_tensor's u8 / 255 in fp32, exactly.  The frames must
-    already have the requested size: the antialiased resize of pose_tensor is a host (PIL) operation."""
+_RESAMPLE = ("bilinear", "bicubic", "lanczos")
+CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)                      # CLIPImageProcessor's image_mean / image_std
+CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def _check_frames(x, what, channels=(3,)):
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] not in channels:
+        raise ValueError(f"{what}: expected uint8 (L, H, W, {' or '.join(map(str, channels))}) frames, got {getattr(x, 'dtype', type(x))} "
+                         f"{tuple(getattr(x, 'shape', ()))}")
+
+
+def resize_frames_device(frames_u8: torch.Tensor, width: int, height: int, resample: str = "bilinear") -> torch.Tensor:
+    """(L, h, w, C) uint8 frames on the device, C = 1 or 3 -> (L, height, width, C) uint8 there: PIL's Image.resize((width, height), resample) of
+    every frame, byte for byte.  resample: "bilinear" (transforms.Resize), "bicubic" (Image.resize's default) or "lanczos"."""
+    from . import conditioning as C
+    _check_frames(frames_u8, "resize_frames_device", (1, 3))
+    if resample not in _RESAMPLE:
+        raise ValueError(f"resize_frames_device: resample {resample!r} is not one of {_RESAMPLE}")
+    if not frames_u8.is_cuda:
+        raise ValueError("resize_frames_device: the frames must be on the device")
+    return C.resize_u8_device(frames_u8.contiguous(), height, width, resample)
+
+
+def pose_tensor_device(frames_u8: torch.Tensor, width: int, height: int, resize: bool = False) -> torch.Tensor:
+    """(L, h, w, 3) uint8 RGB on the device -> (1, 3, L, H, W) float32 in [0, 1] there: pose_tensor's u8 / 255 in fp32, exactly.  Frames of another
+    size raise unless resize=True, which runs pose_tensor's antialiased bilinear resize (PIL's, byte for byte) on the device first."""
+    from . import conditioning as C
     x = frames_u8
-    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError(f"pose_tensor_device: expected uint8 (L, H, W, 3) frames, got {getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
-    if tuple(x.shape[1:3]) != (height, width):
-        raise ValueError(f"pose_tensor_device: the frames are {x.shape[2]} x {x.shape[1]}, the sampler wants {width} x {height}; the antialiased resize "
-                         "is not done on the device: use read_frames + pose_tensor")
+    _check_frames(x, "pose_tensor_device")
+    if tuple(x.shape[1:3]) != (height, width) and not resize:
+        raise ValueError(f"pose_tensor_device: the frames are {x.shape[2]} x {x.shape[1]}, the sampler wants {width} x {height}; pass resize=True for "
+                         "the antialiased resize on the device, or use read_frames + pose_tensor")
     # the 256 quotients come from the host, where pose_tensor divides: a device division by a scalar multiplies by the rounded reciprocal instead
-    lut = (torch.arange(256, dtype=torch.float32) / 255.0).to(x.device)
-    idx = x.permute(3, 0, 1, 2).reshape(-1).to(torch.int32)
-    return torch.index_select(lut, 0, idx).view(1, 3, x.shape[0], height, width)
+    lut = (torch.arange(256, dtype=torch.float32) / 255.0).repeat(3, 1).to(x.device)
+    return C.resize_u8_device(x.contiguous(), height, width, "bilinear", lut=lut)[None]
+
+
+def ref_image_tensors_device(ref_u8: torch.Tensor, width: int, height: int):
+    """The two prologue inputs of the sampler from ONE reference image (h, w, 3) uint8 RGB on the device ->
+      vae_input   (1, 3, height, width) float32 in [-1, 1]: Lanczos resize, u8 / 255 * 2 - 1 -- pipeline._pil_to_tensor(img, width, height, True), exactly;
+      clip_pixels (1, 3, 224, 224) float32: bicubic resize to 224 x 224 (PIL's default filter), then (v / 255 - mean_c) / std_c with CLIP's mean
+                  and std -- CLIPImageProcessor's rescale and normalize in its order of float32 operations.
+    Both float stages are 256-entry tables computed on the host with the host route's own operations; the device only looks them up."""
+    from . import conditioning as C
+    x = ref_u8
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 3 or x.shape[2] != 3 or not x.is_cuda:
+        raise ValueError(f"ref_image_tensors_device: expected a uint8 (h, w, 3) image on the device, got {getattr(x, 'dtype', type(x))} "
+                         f"{tuple(getattr(x, 'shape', ()))}")
+    x = x.contiguous()[None]
+    v = np.arange(256)
+    vae_lut = torch.from_numpy(v.astype(np.float32) / 255.0) * 2.0 - 1.0                       # _pil_to_tensor's operations
+    unit = (v.astype(np.float64) * (1 / 255)).astype(np.float32)                               # the processor rescales in float64, then float32
+    clip_lut = np.stack([(unit - np.float32(m)) / np.float32(s) for m, s in zip(CLIP_MEAN, CLIP_STD)])
+    vae_in = C.resize_u8_device(x, height, width, "lanczos", lut=vae_lut.repeat(3, 1).to(x.device))
+    clip_in = C.resize_u8_device(x, 224, 224, "bicubic", lut=torch.from_numpy(clip_lut).to(x.device))
+    return vae_in.permute(1, 0, 2, 3), clip_in.permute(1, 0, 2, 3)                              # n = 1: the same memory as (1, 3, H, W)
 
 
 def motion_masks_device(face_u8: torch.Tensor, lips_u8: torch.Tensor, hands_u8: Optional[torch.Tensor], length: int, img_size: int = 512):

@@ -9,6 +9,8 @@ Extensions through **kwargs (allowed by the reference signature, :365): `latents
 `clip_image_embeds=` / `ref_image_latents=` / `reference_banks=` / `pose_features=` (hand over prologue results when the module
 is None), `decode=False`, `window_group=` / `cfg_split=` (window-parallel sampling of one long video over several GPUs).
 `context_batch_size=B` runs the window loop B windows per forward: the same sampler as B = 1 (see `denoise`).
+`ref_image` may be a uint8 (h, w, 3) RGB tensor instead of a PIL image: the Lanczos resize in front of the VAE and the bicubic 224 x 224 resize
+in front of CLIP then run on the device (mmgt_amd.inputs.ref_image_tensors_device), with PIL's bytes.
 `output_type="uint8"` returns the frames as uint8 (b, f, H, W, 3), converted on the device (what save_videos_grid writes).
 `output_type="jpeg"` (with `jpeg_quality=`, `jpeg_subsampling=`) returns one JPEG file (bytes) per frame, encoded on the device.
 """
@@ -318,12 +320,19 @@ class Pose2VideoPipeline:
         timesteps = self.scheduler.timesteps
 
         # ---- prologue (once per clip) -------------------------------------------------------------------
+        ref_vae_in = ref_clip_in = None
+        if torch.is_tensor(ref_image):          # a uint8 (h, w, 3) image: both resizes and both float stages on the device
+            from .inputs import ref_image_tensors_device
+            ref_vae_in, ref_clip_in = ref_image_tensors_device(ref_image.to(dev), width, height)
         clip_embeds = kwargs.get("clip_image_embeds")
         if clip_embeds is None:
             if self.image_encoder is None:
                 raise RuntimeError("no image_encoder: pass clip_image_embeds=(1, 768)")
-            from transformers import CLIPImageProcessor
-            clip_image = CLIPImageProcessor().preprocess(ref_image.resize((224, 224)), return_tensors="pt").pixel_values
+            if ref_clip_in is not None:
+                clip_image = ref_clip_in
+            else:
+                from transformers import CLIPImageProcessor
+                clip_image = CLIPImageProcessor().preprocess(ref_image.resize((224, 224)), return_tensors="pt").pixel_values
             clip_embeds = self.image_encoder(clip_image.to(dev, dtype=self.image_encoder.dtype)).image_embeds
         ehs = clip_embeds.to(dev).float().reshape(1, 1, -1)
         encoder_hidden_states = torch.cat([torch.zeros_like(ehs), ehs], dim=0)          # :388-394
@@ -337,7 +346,7 @@ class Pose2VideoPipeline:
                 if not hasattr(self.vae, "encode_mean"):
                     raise RuntimeError("the VAE encoder is not part of this build: pass ref_image_latents=(1,4,h,w) "
                                        "(= vae.encode(ref).latent_dist.mean * 0.18215)")
-                ref_t = _pil_to_tensor(ref_image, width, height, True)[None].to(dev)
+                ref_t = ref_vae_in if ref_vae_in is not None else _pil_to_tensor(ref_image, width, height, True)[None].to(dev)
                 ref_latents = self.vae.encode_mean(ref_t) * 0.18215                      # :427-434
             banks = self.reference_unet.write_banks(ref_latents.to(dev).float().repeat(2, 1, 1, 1), 0,
                                                     encoder_hidden_states)               # :510-520

@@ -12,7 +12,8 @@ pose / mask / audio inputs, everything a pure function of names (mmgt_amd/synthe
 Without --synthetic the inputs are FILES, as in the reference (scripts/pose2vid.py:196-271): the reference image through PIL, the
 pose / mask clips as directories of images, .npy stacks or animated images (mmgt_amd/inputs.py: video containers need PyAV / cv2,
 which this build does not include, and say so), the masks blurred / resampled on the device (mmgt_amd/conditioning.py).  --decoder device
-reads Motion-JPEG .avi clips or directories of .jpg frames on the GPU instead (mmgt_amd/video_in.py).  Weights
+reads Motion-JPEG .avi clips or directories of .jpg frames on the GPU instead (mmgt_amd/video_in.py) and runs the
+resizes of the pose frames and of the reference image there too (PIL's resampling, byte for byte: DESIGN 4f).  Weights
 come from the checkpoints the config yaml names (:137-190) -- or, with --random-weights, from the hash-seeded initialisation (no
 checkpoint exists in this image).  The clip is written as .gif / .npy (mp4 muxing is out of scope: mmgt_amd/video_out.py).
 """
@@ -58,7 +59,8 @@ def parse_args():
                         "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
     p.add_argument("--decoder", default="pil", choices=["pil", "device"],
                    help="how --pose_path and the mask paths are read: pil = on the host (any input read_frames takes); device = Motion-JPEG "
-                        ".avi or a directory of .jpg frames, decoded on the GPU (mmgt_amd.video_in; frames must already be W x H)")
+                        ".avi or a directory of .jpg frames, decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
+                        "resized on the device too (a baseline .jpg is also decoded there)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -162,12 +164,30 @@ def load_inputs(a, dev):
     if L < a.L:
         print(f"note: {L} usable frames < L = {a.L}: sampling {L} frames")
     if device:
-        pose = inputs.pose_tensor_device(pose_frames[:L], a.W, a.H)           # stays on the device: the pipeline moves it there anyway
+        pose = inputs.pose_tensor_device(pose_frames[:L], a.W, a.H, resize=True)   # any frame size: PIL's bilinear resize on the device
         full, face, lips = inputs.motion_masks_device(face_frames, lips_frames, hands_frames, L, a.H)
     else:
         pose = inputs.pose_tensor(pose_frames[:L], a.W, a.H)
         full, face, lips = inputs.motion_masks(face_frames, lips_frames, hands_frames, L, dev, a.H)
     return pose, full, face, lips, L
+
+
+def load_ref_image(a, dev):
+    """The reference image as the pipeline takes it: a PIL image, or with --decoder device a uint8 (h, w, 3) tensor on the device -- a baseline
+    .jpg is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
+    from PIL import Image
+    if getattr(a, "decoder", "pil") != "device":
+        return Image.open(a.image_path).convert("RGB")
+    if os.path.splitext(a.image_path)[1].lower() in (".jpg", ".jpeg"):
+        from mmgt_amd.video_in import decode_jpeg_frames
+        with open(a.image_path, "rb") as fh:
+            data = fh.read()
+        try:
+            return decode_jpeg_frames([data], dev)[0]
+        except ValueError as e:                                  # outside the device decoder's scope (progressive, CMYK, ...): parse_jpeg says why
+            print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
+    import numpy as np
+    return torch.from_numpy(np.asarray(Image.open(a.image_path).convert("RGB")).copy()).to(dev)
 
 
 def run_files(a, dev, dtype):
@@ -180,7 +200,7 @@ def run_files(a, dev, dtype):
     t0 = time.time()
     pipe = build_synthetic(dev, dtype) if a.random_weights else build_from_checkpoints(a.config, a.num_c, dev, dtype)
     t_build = time.time() - t0
-    ref_img = Image.open(a.image_path).convert("RGB")
+    ref_img = load_ref_image(a, dev)
     pose, full, face, lips, L = load_inputs(a, dev)
     audio = torch.zeros(1, L, 32, 768)                        # pose2vid runs with null audio (:279)
     gen = torch.manual_seed(a.seed)
