@@ -457,6 +457,31 @@ int mmgt_gif_strip_stride(int W, int strip_rows, long* stride);
  * packed_stride >= B + ceil(B / 255) + 1 with B = strips * out_stride. */
 int mmgt_gif_pack(const unsigned char* out, const long long* bits, unsigned char* packed, int* sizes, int n, int strips, long out_stride,
                   long packed_stride, void* stream);
+/* ---- PNG output path (csrc/png.hip, mmgt_amd/video_out.py): the zlib / deflate image data of truecolour 8-bit PNG frames.  Every buffer
+ * is a device pointer.  Like every entry: 0 on success, else mmgt_last_error() has the text and nothing was launched.
+ * filter: frames (n, H, W, 3) u8 RGB -> filt (n, H, 1 + 3 W): per scanline the filter type (the smallest sum of min(v, 256 - v) over the filtered
+ * bytes, the lowest type on a tie; bpp = 3, the row above row 0 is zeros) and the filtered row; sums (n, H, 2) = { sum d[i], sum (L - i) d[i] } over
+ * the row's L = 1 + 3 W bytes, of which the host makes the Adler-32.  n, H, W >= 1, H, W <= 16384. */
+int mmgt_png_filter(const unsigned char* frames, unsigned char* filt, long long* sums, int n, int H, int W, void* stream);
+/* The two passes of the deflate coder over ANY bytes: data (n, frame_bytes), every row cut into strips = ceil(frame_bytes / strip_bytes) strips of
+ * strip_bytes (the last may be shorter), 1 <= frame_bytes <= 2^30.  A strip's tokens: position 0 is a literal; at p >= 1 with r = bytes from p on that
+ * equal byte p - 1 (at most 258), r >= 3 is a match of length r and distance 1, else byte p is a literal; symbol 256 closes the strip.
+ * histogram: hist (n * strips, 286) = how often each literal/length symbol occurs (every entry is written).
+ * deflate: strip k = frame * strips + s writes header_bits[k] <= 8 * MMGT_PNG_HEADER_BYTES bits of header + k * MMGT_PNG_HEADER_BYTES, then its tokens
+ * coded with codes + k * 286 (entry = the symbol's code, bit-reversed for an LSB-first stream, | its length << 16; a match is followed by its extra
+ * bits and one zero bit, the single distance code), LSB-first into the words slot_off[k] .. slot_off[k + 1] - 1 of slots (slot_off has n * strips + 1
+ * entries; no word outside a slot or outside slots_words is touched, every word below ceil(bits / 32) of a slot is written), and bits[k] = the bits
+ * it took. */
+#define MMGT_PNG_HEADER_BYTES 576
+int mmgt_png_histogram(const unsigned char* data, unsigned int* hist, int n, long long frame_bytes, long long strip_bytes, void* stream);
+int mmgt_png_deflate(const unsigned char* data, const unsigned int* codes, const unsigned int* header, const int* header_bits, unsigned int* slots,
+                     const long long* slot_off, long long slots_words, long long* bits, int n, long long frame_bytes, long long strip_bytes,
+                     void* stream);
+/* Joins the strips of each frame bit by bit: bit_off (n, strips + 1) = where strip s starts in frame f's stream and, last, where the stream ends;
+ * frame f's bytes go to out[out_off[f] .. out_off[f + 1] - 1] (out_off has n + 1 entries), every one of them written, the bits past the end zero.
+ * Nothing outside slots_words / out_bytes is read or written. */
+int mmgt_png_pack(const unsigned int* slots, const long long* slot_off, long long slots_words, const long long* bit_off, unsigned char* out,
+                  const long long* out_off, long long out_bytes, int n, int strips, void* stream);
 /* SMGA key points -> the four frame streams of Stage 2, drawn on the device: kp (frames, 134, 3) fp32 = SMGA's normalised
  * (x, y, score) features.  Replaces data/extract_movment_mask_all.py:319-321 `pose_vid_generator` (denormalize :128-132, mask_leg :66-89,
  * process_keypoints :98-119), src/dwpose/__init__.py:220-283 `DWposeDetector_movment_mask.__call__` with draw_pose / draw_pose_mask_head /

@@ -124,6 +124,11 @@ _SIGS = {
     "mmgt_gif_lzw": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p]),
     "mmgt_gif_strip_stride": (c_int, [c_int, c_int, ctypes.POINTER(c_long)]),
     "mmgt_gif_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_void_p]),
+    "mmgt_png_filter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_png_histogram": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
+    "mmgt_png_deflate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong,
+                                 ctypes.c_longlong, c_void_p]),
+    "mmgt_png_pack": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
@@ -1231,6 +1236,101 @@ def gif_pack(slots, bits, out=None):
     _check(lib().mmgt_gif_pack(_ptr(slots), _ptr(bits), _ptr(packed), _ptr(sizes), n, strips, slots.stride(0), packed.stride(0), _stream()),
            "mmgt_gif_pack")
     return packed, sizes
+
+
+# ------------------------------------------------------------------------------------------------------------ PNG (csrc/png.hip)
+
+PNG_SYMS = 286
+PNG_HEADER_BYTES = 576              # MMGT_PNG_HEADER_BYTES: room for the longest dynamic-Huffman block header
+
+
+def png_filter(frames, out=None):
+    """(n, H, W, 3) uint8 RGB -> (filt (n, H, 1 + 3 W) uint8, sums (n, H, 2) int64): every scanline's filter type byte and filtered bytes, and the
+    two sums of which the host makes the row's Adler-32 (see mmgt_png_filter).  `out` = (filt, sums) to write into."""
+    n, H, W = _gif_frames(frames, "png_filter")
+    if out is None:
+        out = (torch.empty((n, H, 1 + 3 * W), device=frames.device, dtype=torch.uint8),
+               torch.empty((n, H, 2), device=frames.device, dtype=torch.int64))
+    filt, sums = out
+    assert filt.shape == (n, H, 1 + 3 * W) and filt.dtype == torch.uint8 and filt.is_contiguous()
+    assert sums.shape == (n, H, 2) and sums.dtype == torch.int64 and sums.is_contiguous()
+    _check(lib().mmgt_png_filter(_ptr(frames), _ptr(filt), _ptr(sums), n, H, W, _stream()), "mmgt_png_filter")
+    return filt, sums
+
+
+def _png_data(data, strip_bytes, what):
+    _dev(data)
+    if data.dtype != torch.uint8 or data.dim() != 2 or not data.is_contiguous() or data.shape[0] < 1 or data.shape[1] < 1 or int(strip_bytes) < 1:
+        raise RuntimeError(f"{what}: data must be contiguous uint8 (n, frame_bytes), strip_bytes at least 1")
+    n, frame_bytes = data.shape
+    return n, frame_bytes, -(-frame_bytes // int(strip_bytes))
+
+
+def png_histogram(data, strip_bytes, out=None):
+    """data (n, frame_bytes) uint8, any bytes -> (n, strips, 286): how often each literal/length symbol occurs in the tokens of every strip of
+    strip_bytes bytes (see mmgt_png_histogram).  The counts are uint32 held in an int32 tensor."""
+    n, frame_bytes, strips = _png_data(data, strip_bytes, "png_histogram")
+    if out is None:
+        out = torch.empty((n, strips, PNG_SYMS), device=data.device, dtype=torch.int32)
+    assert out.shape == (n, strips, PNG_SYMS) and out.dtype == torch.int32 and out.is_contiguous()
+    _check(lib().mmgt_png_histogram(_ptr(data), _ptr(out), n, frame_bytes, int(strip_bytes), _stream()), "mmgt_png_histogram")
+    return out
+
+
+def png_slot_offsets(want_bits):
+    """Exact bit counts (n, strips) -> word offsets (n * strips + 1,) int64 of slots that hold them, each a whole number of 32-bit words."""
+    import numpy as np
+    w = np.asarray(want_bits, np.int64).reshape(-1)
+    if w.size == 0 or (w < 1).any():
+        raise RuntimeError("png: every strip holds at least one bit")
+    return np.concatenate([[0], np.cumsum((w + 31) // 32)]).astype(np.int64)
+
+
+def png_deflate(data, strip_bytes, codes, headers, header_bits, want_bits, out=None):
+    """Codes every strip of data (n, frame_bytes) into its slot: host arrays codes (n, strips, 286) uint32, headers (n, strips, PNG_HEADER_BYTES)
+    uint8, header_bits (n, strips) int32 and want_bits (n, strips) int64, the bit count of each strip that sizes and places its slot
+    (png_slot_offsets) -> (slots (words,) int32, bits (n, strips) int64 as the device counted them).  `out` = (slots, bits) to write into."""
+    import numpy as np
+    n, frame_bytes, strips = _png_data(data, strip_bytes, "png_deflate")
+    codes, headers = np.ascontiguousarray(codes, np.uint32), np.ascontiguousarray(headers, np.uint8)
+    header_bits, off = np.ascontiguousarray(header_bits, np.int32), png_slot_offsets(want_bits)
+    if codes.shape != (n, strips, PNG_SYMS) or headers.shape != (n, strips, PNG_HEADER_BYTES) or header_bits.shape != (n, strips) or \
+            off.size != n * strips + 1 or header_bits.min() < 0 or header_bits.max() > 8 * PNG_HEADER_BYTES:
+        raise RuntimeError(f"png_deflate: tables do not match {n} x {strips} strips")
+    up = lambda a, dt: torch.from_numpy(a.view(dt)).to(data.device)
+    if out is None:
+        out = (torch.empty((int(off[-1]),), device=data.device, dtype=torch.int32),
+               torch.empty((n, strips), device=data.device, dtype=torch.int64))
+    slots, bits = out
+    assert slots.dim() == 1 and slots.numel() >= int(off[-1]) and slots.dtype == torch.int32 and slots.is_contiguous()
+    assert bits.shape == (n, strips) and bits.dtype == torch.int64 and bits.is_contiguous()
+    codes, headers, header_bits, off = up(codes, np.int32), up(headers, np.uint8), up(header_bits, np.int32), up(off, np.int64)    # alive until launched
+    _check(lib().mmgt_png_deflate(_ptr(data), _ptr(codes), _ptr(headers), _ptr(header_bits), _ptr(slots), _ptr(off), slots.numel(), _ptr(bits), n,
+                                  frame_bytes, int(strip_bytes), _stream()), "mmgt_png_deflate")
+    return slots, bits
+
+
+def png_pack(slots, want_bits, out=None):
+    """The slots of png_deflate, laid out by the same want_bits (n, strips) -> (packed (bytes,) uint8, out_off (n + 1,) host int64): frame f's
+    deflate stream, its strips joined bit by bit, is packed[out_off[f]:out_off[f + 1]].  `out` = packed to write into."""
+    import numpy as np
+    _dev(slots)
+    w = np.asarray(want_bits, np.int64)
+    n, strips = w.shape
+    off = png_slot_offsets(w)
+    bit_off = np.concatenate([np.zeros((n, 1), np.int64), np.cumsum(w, axis=1)], axis=1)
+    out_off = np.concatenate([[0], np.cumsum((bit_off[:, -1] + 7) // 8)]).astype(np.int64)
+    if out is None:
+        out = torch.empty((int(out_off[-1]),), device=slots.device, dtype=torch.uint8)
+    assert slots.dim() == 1 and slots.numel() >= int(off[-1]) and slots.dtype == torch.int32 and slots.is_contiguous()
+    assert out.dim() == 1 and out.numel() >= int(out_off[-1]) and out.dtype == torch.uint8 and out.is_contiguous()
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(slots.device)
+    for f0 in range(0, n, 65535):                                  # the launch's grid holds a frame per y index
+        f1 = min(n, f0 + 65535)
+        d_off, d_bit, d_out = up(off[f0 * strips:f1 * strips + 1]), up(bit_off[f0:f1]), up(out_off[f0:f1 + 1])                      # alive until launched
+        _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, strips,
+                                   _stream()), "mmgt_png_pack")
+    return out, out_off
 
 
 def dwpose_draw(kp, H=512, W=512):

@@ -5,7 +5,8 @@ encodes with PyAV / libx264, which is not part of this build: .gif goes through 
 .npy stores the raw uint8 frames, .mp4 raises.  .avi is this build's video file: baseline JPEG frames encoded on the device
 (csrc/mjpeg.hip; encode_jpeg_frames) in a RIFF AVI 1.0 container with an optional PCM sound track (write_avi).  gif_encoder="device" is a second,
 opt-in .gif writer: one palette for the clip (gif_palette, gif_lut), index map, LZW and sub-block packing on the device (csrc/gif.hip;
-encode_gif_frames) and the GIF89a container here (write_gif)."""
+encode_gif_frames) and the GIF89a container here (write_gif).  .apng / .png are the lossless output: scanline filters and deflate on the device
+(csrc/png.hip; encode_png_frames), Huffman code lengths, block headers and the PNG / APNG chunks here (write_png, write_png_sequence, write_apng)."""
 import os
 import struct
 from pathlib import Path
@@ -342,6 +343,293 @@ def write_gif(path, palette, frame_blobs, W, H, fps, loop=0):
     return len(body)
 
 
+# ---- PNG / APNG: lossless frames, filtered and deflated on the device ---------------------------------------------------------------
+PNG_STRIP_ROWS = 64                 # scanlines per deflate block of encode_png_frames: the strip_rows sweep of tools/bench_png.py
+PNG_SCRATCH_BYTES = 256 << 20       # encode_png_frames holds at most this much filtered rows, strip slots and tables per set of launches
+PNG_MAX_SIDE = 16384
+_ADLER = 65521
+_CL_ORDER = np.array([16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15])
+# extra bits of the literal/length symbols 0 .. 285 (RFC 1951 3.2.5)
+_LEN_EXTRA = np.zeros(286, np.int64)
+_LEN_EXTRA[265:285] = np.repeat(np.arange(1, 6), 4)
+
+
+def deflate_code_lengths(hist, max_bits) -> np.ndarray:
+    """Counts per symbol -> optimal code lengths of at most max_bits, by package-merge.  The used symbols are the leaves, sorted by (count, symbol).
+    List 1 is the leaves; list k + 1 merges the leaves with the packages of list k (its items paired in order, an odd last one dropped) by weight,
+    at equal weight every leaf before every package.  The first 2 m - 2 items of list max_bits (m = used symbols) are taken; a symbol's length is
+    the number of lists in which its leaf is among the items taken, where taking a package takes the two items it was made of.  Only the weights
+    and which item is a leaf are kept: the leaves taken from a list are always its first ones.  One used symbol gets length 1."""
+    h = np.asarray(hist).astype(np.int64).reshape(-1)
+    max_bits = int(max_bits)
+    if (h < 0).any():
+        raise ValueError("deflate_code_lengths: counts must not be negative")
+    order = np.flatnonzero(h)
+    order = order[np.argsort(h[order], kind="stable")]                    # (count, symbol)
+    m = order.size
+    lengths = np.zeros(h.size, np.int64)
+    if m == 1:
+        lengths[order[0]] = 1
+    if m < 2:
+        return lengths
+    if max_bits < 1 or m > (1 << max_bits):
+        raise ValueError(f"deflate_code_lengths: {m} symbols do not fit codes of {max_bits} bits")
+    w = h[order]
+    leaf_flags = [np.ones(m, bool)]                                          # per list: which of its items are leaves
+    cur = w
+    for _ in range(max_bits - 1):
+        pk = cur[0:cur.size - 1:2] + cur[1:cur.size:2]
+        pos = np.searchsorted(w, pk, side="right") + np.arange(pk.size)      # a package stands after the leaves of its weight
+        flags = np.ones(m + pk.size, bool)
+        flags[pos] = False
+        nxt = np.empty(m + pk.size, np.int64)
+        nxt[pos] = pk
+        nxt[flags] = w
+        leaf_flags.append(flags)
+        cur = nxt
+    take = 2 * m - 2
+    depth = np.zeros(m + 1, np.int64)
+    for flags in reversed(leaf_flags):
+        leaves = int(np.count_nonzero(flags[:take]))
+        depth[0] += 1
+        depth[leaves] -= 1
+        take = 2 * (take - leaves)
+        if take == 0:
+            break
+    lengths[order] = np.cumsum(depth)[:m]
+    return lengths
+
+
+_REV16 = np.zeros(1 << 16, np.int64)
+for _b in range(16):
+    _REV16 |= ((np.arange(1 << 16) >> _b) & 1) << (15 - _b)
+
+
+def _canonical_codes(lengths):
+    """RFC 1951 3.2.2 -> the codes, already bit-reversed for an LSB-first writer."""
+    lengths = np.asarray(lengths, np.int64)
+    count = np.bincount(lengths, minlength=17)
+    first = np.concatenate([[0], np.cumsum(count)])                          # where each length starts among the symbols sorted by (length, symbol)
+    count[0] = 0
+    nxt = np.zeros(17, np.int64)
+    for b in range(1, 17):
+        nxt[b] = (nxt[b - 1] + count[b - 1]) << 1
+    idx = np.argsort(lengths, kind="stable")
+    ls = lengths[idx]
+    code = np.zeros(lengths.size, np.int64)
+    code[idx] = nxt[ls] + np.arange(lengths.size) - first[ls]
+    return np.where(lengths > 0, _REV16[code & 0xFFFF] >> (16 - lengths), 0)
+
+
+def _rle_code_lengths(seq):
+    """The code lengths as (symbol, extra bits, extra value) of the code-length alphabet.  Zeros: 18 for min(run, 138) while 11 or more are left,
+    then 17 for 3 .. 10, then single zeros; a non-zero length: itself, then 16 for min(rest, 6) while 3 or more are left, then itself."""
+    seq = np.asarray(seq)
+    cut = np.flatnonzero(np.diff(seq)) + 1
+    starts = np.concatenate([[0], cut])
+    runs = np.diff(np.concatenate([starts, [seq.size]]))
+    out = []
+    for v, run in zip(seq[starts].tolist(), runs.tolist()):
+        if v == 0:
+            while run >= 11:
+                k = min(run, 138)
+                out.append((18, 7, k - 11))
+                run -= k
+            if run >= 3:
+                out.append((17, 3, run - 3))
+                run = 0
+        else:
+            out.append((v, 0, 0))
+            run -= 1
+            while run >= 3:
+                k = min(run, 6)
+                out.append((16, 2, k - 3))
+                run -= k
+        out += [(v, 0, 0)] * run
+    return out
+
+
+def deflate_block_header(litlen_lengths, dist_lengths, final):
+    """The head of a dynamic-Huffman block (RFC 1951 3.2.7) as an LSB-first bit string: BFINAL, BTYPE = 10, HLIT, HDIST, HCLEN, the code-length
+    code's lengths in the permuted order, then the literal/length and distance code lengths coded with it (runs as 16 / 17 / 18, which may cross
+    from one alphabet into the other).  -> (bytes, bit count); the bits past the count are zero."""
+    ll = np.asarray(litlen_lengths, np.int64)
+    dl = np.asarray(dist_lengths, np.int64)
+    if ll.size != 286 or not 1 <= dl.size <= 30 or ll[256] == 0:
+        raise ValueError("deflate_block_header: 286 literal/length code lengths with symbol 256 used, and 1 .. 30 distance code lengths")
+    nll = max(257, int(np.flatnonzero(ll)[-1]) + 1)
+    syms = _rle_code_lengths(np.concatenate([ll[:nll], dl]))
+    cl = deflate_code_lengths(np.bincount([s for s, _, _ in syms], minlength=19), 7)
+    codes = _canonical_codes(cl)
+    ncl = max(4, int(np.flatnonzero(cl[_CL_ORDER])[-1]) + 1)
+    acc, nb = (1 if final else 0) | 2 << 1 | (nll - 257) << 3 | (dl.size - 1) << 8 | (ncl - 4) << 13, 17
+    for k in range(ncl):
+        acc |= int(cl[_CL_ORDER[k]]) << nb
+        nb += 3
+    cl, codes = cl.tolist(), codes.tolist()
+    for s, eb, ev in syms:
+        acc |= (codes[s] | ev << cl[s]) << nb
+        nb += cl[s] + eb
+    return acc.to_bytes((nb + 7) // 8, "little"), nb
+
+
+def adler32_combine(adler1, adler2, len2) -> int:
+    """Adler-32 of A + B from those of A and B and len(B), as zlib's adler32_combine."""
+    a1, b1, a2, b2 = adler1 & 0xFFFF, adler1 >> 16 & 0xFFFF, adler2 & 0xFFFF, adler2 >> 16 & 0xFFFF
+    if len2 < 0:
+        raise ValueError("adler32_combine: negative length")
+    return ((b1 + b2 + (len2 % _ADLER) * (a1 + _ADLER - 1)) % _ADLER) << 16 | (a1 + a2 + _ADLER - 1) % _ADLER
+
+
+def png_strip_tables(hist, final):
+    """One strip's histogram of the 286 literal/length symbols -> (codes u32[286] = bit-reversed code | length << 16, header bytes, header bits,
+    bits of the whole block)."""
+    ll = deflate_code_lengths(hist, 15)
+    matches = int(hist[257:].sum())
+    head, hbits = deflate_block_header(ll, [1 if matches else 0], final)
+    table = (_canonical_codes(ll) | ll << 16).astype(np.uint32)
+    return table, head, hbits, hbits + int((hist * (ll + _LEN_EXTRA)).sum()) + matches
+
+
+def encode_png_frames(frames_u8, strip_rows=None) -> list:
+    """(n, H, W, 3) uint8 RGB frames (a CUDA tensor, or host data that is uploaded) -> n byte strings, each the zlib stream of one frame's PNG image
+    data (write_png / write_apng put the chunks around it).  Filter choice, tokens, Huffman coding and bit packing run on the device
+    (csrc/png.hip); the host builds each strip's codes and block header from the device's symbol histograms, knows every strip's bit count from
+    them, and receives the Adler-32 sums of the rows and ONE buffer of finished bytes per set of launches.  The bytes are the same on every call;
+    DESIGN.md 4g defines them."""
+    from . import hip
+    x = torch.as_tensor(frames_u8)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"encode_png_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
+    n, H, W, _ = x.shape
+    if n == 0 or H == 0 or W == 0:
+        raise ValueError(f"encode_png_frames: empty clip {tuple(x.shape)}")
+    if H > PNG_MAX_SIDE or W > PNG_MAX_SIDE:
+        raise ValueError(f"encode_png_frames: a frame is at most {PNG_MAX_SIDE} x {PNG_MAX_SIDE}, got {W} x {H}")
+    strip_rows = int(PNG_STRIP_ROWS if strip_rows is None else strip_rows)
+    if strip_rows < 1:
+        raise ValueError(f"encode_png_frames: strip_rows must be at least 1, got {strip_rows}")
+    strip_rows = min(strip_rows, H)
+    if not x.is_cuda:
+        x = x.cuda()
+    x = x.contiguous()
+    rowlen = 1 + 3 * W
+    strips = -(-H // strip_rows)
+    # filtered rows; slots and output, each at most 15 bits a byte and a header per strip; histograms, code tables, headers and offsets
+    per_frame = 5 * H * rowlen + strips * (2 * 286 * 4 + 3 * hip.PNG_HEADER_BYTES + 64)
+    per_call = max(1, PNG_SCRATCH_BYTES // per_frame)
+    blobs = []
+    for f0 in range(0, n, per_call):
+        filt, sums = hip.png_filter(x[f0:f0 + per_call])
+        raw = deflate_strips_device(filt.view(filt.shape[0], H * rowlen), strip_rows * rowlen)
+        for body, rows in zip(raw, sums.cpu().numpy().tolist()):
+            adler = 1
+            for s1, s2 in rows:                                                  # a row's sum of d[i] and of (rowlen - i) d[i]
+                adler = adler32_combine(adler, ((rowlen + s2) % _ADLER) << 16 | (1 + s1) % _ADLER, rowlen)
+            blobs.append(b"\x78\x01" + body + struct.pack(">I", adler))
+    return blobs
+
+
+def deflate_strips_device(data, strip_bytes) -> list:
+    """(k, frame_bytes) uint8 on the device, any bytes -> k raw deflate streams (no zlib wrapper): every row cut into strips of strip_bytes (the
+    last may be shorter), each strip one dynamic-Huffman block of distance-1 matches and literals.  Two passes over the bytes: symbol histograms
+    per strip (down), codes and block headers (host, up), then coding into exactly sized slots and joining them at bit offsets."""
+    from . import hip
+    k, strips = data.shape[0], -(-data.shape[1] // int(strip_bytes))
+    hist = hip.png_histogram(data, strip_bytes).cpu().numpy().view(np.uint32).astype(np.int64)                   # (k, strips, 286)
+    codes = np.empty((k, strips, 286), np.uint32)
+    heads, hbits = np.zeros((k, strips, hip.PNG_HEADER_BYTES), np.uint8), np.empty((k, strips), np.int32)
+    want = np.empty((k, strips), np.int64)
+    seen = {}                                                                # flat and pose-like clips repeat a few histograms many times
+    for f in range(k):
+        for s in range(strips):
+            key = (hist[f, s].tobytes(), s == strips - 1)
+            if key not in seen:
+                seen[key] = png_strip_tables(hist[f, s], s == strips - 1)
+            codes[f, s], head, hbits[f, s], want[f, s] = seen[key]
+            heads[f, s, :len(head)] = np.frombuffer(head, np.uint8)
+    slots, bits = hip.png_deflate(data, strip_bytes, codes, heads, hbits, want)
+    packed, out_off = hip.png_pack(slots, want)
+    bits = bits.cpu().numpy()
+    if not np.array_equal(bits, want):
+        bad = tuple(np.argwhere(bits != want)[0])
+        raise RuntimeError(f"deflate_strips_device: strip {bad} took {bits[bad]} bits on the device, its histogram gives {want[bad]} "
+                           "(mmgt_png_deflate)")
+    packed = packed.cpu().numpy()
+    return [packed[out_off[f]:out_off[f + 1]].tobytes() for f in range(k)]
+
+
+def _png_chunk(kind: bytes, body: bytes) -> bytes:
+    import zlib
+    return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body))
+
+
+_PNG_SIG = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_ihdr(W, H, what):
+    W, H = int(W), int(H)
+    if not (1 <= W <= PNG_MAX_SIDE and 1 <= H <= PNG_MAX_SIDE):
+        raise ValueError(f"{what}: a frame is 1 .. {PNG_MAX_SIDE} pixels a side, got {W} x {H}")
+    return _png_chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))      # 8 bit, truecolour, deflate, adaptive filtering, no interlace
+
+
+def _write(path, body):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(body)
+    return len(body)
+
+
+def write_png(path, blob, W, H):
+    """One frame of encode_png_frames -> a PNG file: signature, IHDR, one IDAT, IEND.  Returns the bytes written."""
+    return _write(path, _PNG_SIG + _png_ihdr(W, H, "write_png") + _png_chunk(b"IDAT", bytes(blob)) + _png_chunk(b"IEND", b""))
+
+
+def write_png_sequence(directory, blobs, W, H):
+    """0000.png, 0001.png, ... in `directory` (what `ffmpeg -i %04d.png` reads).  Returns the paths."""
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise ValueError("write_png_sequence: no frames")
+    paths = [os.path.join(str(directory), f"{k:04d}.png") for k in range(len(blobs))]
+    for p, b in zip(paths, blobs):
+        write_png(p, b, W, H)
+    return paths
+
+
+def write_apng(path, blobs, W, H, fps, loop=0):
+    """APNG 1.0: IHDR, acTL (frames, `loop` plays, 0 = for ever), then per frame one fcTL covering the whole frame at offset 0 with the delay
+    Fraction(1 / fps).limit_denominator(65535) seconds, dispose and blend 0; frame 0's data in IDAT, every later frame's in fdAT; fcTL and fdAT
+    carry consecutive sequence numbers from 0.  With one frame no animation chunks are written: the file is an ordinary PNG.  Returns the bytes
+    written."""
+    from fractions import Fraction
+    blobs = [bytes(b) for b in blobs]
+    if not blobs:
+        raise ValueError("write_apng: no frames")
+    if not float(fps) > 0:
+        raise ValueError(f"write_apng: fps must be positive, got {fps}")
+    loop = int(loop)
+    if not 0 <= loop < 1 << 31:
+        raise ValueError(f"write_apng: loop must be 0 .. 2^31 - 1, got {loop}")
+    ihdr = _png_ihdr(W, H, "write_apng")
+    if len(blobs) == 1:
+        return write_png(path, blobs[0], W, H)
+    delay = Fraction(1 / float(fps)).limit_denominator(65535)
+    if delay.numerator > 65535:
+        raise ValueError(f"write_apng: a frame's delay is at most 65535 s, got fps = {fps}")
+    out, seq = [_PNG_SIG, ihdr, _png_chunk(b"acTL", struct.pack(">II", len(blobs), loop))], 0
+    for k, b in enumerate(blobs):
+        out.append(_png_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, int(W), int(H), 0, 0, delay.numerator, delay.denominator, 0, 0)))
+        seq += 1
+        if k == 0:
+            out.append(_png_chunk(b"IDAT", b))
+        else:
+            out.append(_png_chunk(b"fdAT", struct.pack(">I", seq) + b))
+            seq += 1
+    out.append(_png_chunk(b"IEND", b""))
+    return _write(path, b"".join(out))
+
+
 def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90, gif_encoder="pil"):
     if gif_encoder not in ("pil", "device"):
         raise ValueError(f"gif_encoder must be 'pil' or 'device', got {gif_encoder!r}")
@@ -366,6 +654,8 @@ def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=
         np.save(path, frames)
     elif fmt == ".avi":
         write_avi(path, encode_jpeg_frames(frames, quality), frames.shape[2], frames.shape[1], fps)
+    elif fmt in (".apng", ".png"):                                          # lossless; one frame gives an ordinary PNG
+        write_apng(path, encode_png_frames(frames), frames.shape[2], frames.shape[1], fps)
     elif fmt == ".mp4":
         raise RuntimeError("mp4 output needs PyAV / libx264 (src/utils/util.py:83-97), which this build does not include: "
                            "write .gif or .npy, or hand frames_uint8() to your encoder")

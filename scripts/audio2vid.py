@@ -57,8 +57,9 @@ def parse_args():
     p.add_argument("--motion_diffusion_ckpt", type=str, default="./pretrained_weights/MMGT_pretrained/stage_1/audio2pose_best_model.pt")
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--format", default="npy", choices=["npy", "gif", "avi"],
-                   help="avi = Motion-JPEG encoded on the device, with the samples of --audio_path as its PCM sound track")
+    p.add_argument("--format", default="npy", choices=["npy", "gif", "avi", "apng", "pngs"],
+                   help="avi = Motion-JPEG encoded on the device, with the samples of --audio_path as its PCM sound track; apng = lossless animated "
+                        "PNG, pngs = a directory of 0000.png, 0001.png, ..., both filtered and deflated on the device (mmgt_amd.video_out)")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
@@ -252,6 +253,10 @@ def main():
         sound = read_wav_pcm(a.audio_path, a.L / fps) if a.audio_path else None
         extra["bytes"] = write_avi(path, jpegs, a.W, a.H, fps, audio=sound)
         extra["encode_s"] = round(time.time() - t0, 3)
+    elif a.format == "pngs":                               # a directory that `ffmpeg -i %04d.png` reads
+        from mmgt_amd.video_out import encode_png_frames, write_png_sequence
+        path = os.path.splitext(path)[0] + "_png"
+        extra["files"] = len(write_png_sequence(path, encode_png_frames(v[0]), a.W, a.H))
     else:
         save_videos_grid(v, path, n_rows=1, fps=a.fps or 25, gif_encoder=a.gif_encoder)
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,

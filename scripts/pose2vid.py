@@ -15,7 +15,8 @@ which this build does not include, and say so), the masks blurred / resampled on
 reads Motion-JPEG .avi clips or directories of .jpg frames on the GPU instead (mmgt_amd/video_in.py) and runs the
 resizes of the pose frames and of the reference image there too (PIL's resampling, byte for byte: DESIGN 4f).  Weights
 come from the checkpoints the config yaml names (:137-190) -- or, with --random-weights, from the hash-seeded initialisation (no
-checkpoint exists in this image).  The clip is written as .gif / .npy (mp4 muxing is out of scope: mmgt_amd/video_out.py).
+checkpoint exists in this image).  The clip is written as .gif / .npy / Motion-JPEG .avi / lossless .apng or a directory of .png files (mp4 muxing is out of scope:
+mmgt_amd/video_out.py).
 """
 import argparse
 import json
@@ -51,8 +52,10 @@ def parse_args():
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--random-weights", action="store_true",
                    help="file inputs with the hash-seeded random initialisation instead of the checkpoints of --config")
-    p.add_argument("--format", default="gif", choices=["gif", "npy", "avi"],
-                   help="output container of the file-input mode; avi = Motion-JPEG encoded on the device (mmgt_amd.video_out)")
+    p.add_argument("--format", default="gif", choices=["gif", "npy", "avi", "apng", "pngs"],
+                   help="output container of the file-input mode; avi = Motion-JPEG encoded on the device; apng = lossless animated PNG, pngs = a "
+                        "directory of 0000.png, 0001.png, ..., both filtered and deflated on the device (mmgt_amd.video_out); with --synthetic, "
+                        "apng / pngs also write the clip that way")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
@@ -218,6 +221,11 @@ def run_files(a, dev, dtype):
         from mmgt_amd.video_out import write_avi
         extra = {"bytes": write_avi(path, out.videos, a.W, a.H, a.fps), "quality": a.quality}
         shape = [1, len(out.videos), a.H, a.W, 3]
+    elif a.format == "pngs":                                  # a directory that `ffmpeg -i %04d.png` reads
+        from mmgt_amd.video_out import encode_png_frames, frames_uint8, write_png_sequence
+        path = os.path.splitext(path)[0] + "_png"
+        extra = {"files": len(write_png_sequence(path, encode_png_frames(frames_uint8(out.videos, 1)), a.W, a.H))}
+        shape = list(torch.as_tensor(out.videos).shape)
     else:
         save_videos_grid(out.videos, path, n_rows=1, fps=a.fps, gif_encoder=a.gif_encoder)
         shape = list(torch.as_tensor(out.videos).shape)
@@ -300,6 +308,16 @@ def main():
         extra["gif"] = os.path.splitext(path)[0] + ".gif"
         save_videos_grid(v, extra["gif"], n_rows=1, fps=a.fps, gif_encoder="device")
         extra["gif_bytes"] = os.path.getsize(extra["gif"])
+    if a.format == "apng" and not a.no_decode:
+        from mmgt_amd.video_out import save_videos_grid
+        extra["apng"] = os.path.splitext(path)[0] + ".apng"
+        save_videos_grid(v, extra["apng"], n_rows=1, fps=a.fps)
+        extra["apng_bytes"] = os.path.getsize(extra["apng"])
+    if a.format == "pngs" and not a.no_decode:
+        from mmgt_amd.video_out import encode_png_frames, frames_uint8, write_png_sequence
+        extra["pngs"] = os.path.splitext(path)[0] + "_png"
+        frames = frames_uint8(v, 1)
+        extra["png_files"] = len(write_png_sequence(extra["pngs"], encode_png_frames(frames), frames.shape[2], frames.shape[1]))
     print(json.dumps({"video": list(v.shape), "saved": path, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "windows_per_step": len(list(__import__("mmgt_amd.context", fromlist=["uniform"]).uniform(
                           0, a.steps, a.L, a.num_c, 1, 4))), "context_batch_size": a.context_batch_size, "dtype": a.dtype,
