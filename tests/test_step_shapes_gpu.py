@@ -11,6 +11,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from mmgt_amd.synthetic import hash_uniform  # noqa: E402
+from tests import mm_gate  # noqa: E402
 
 DEV = "cuda:0"
 ULP = 2.0 ** -8
@@ -27,6 +28,14 @@ def check(out, ref, acc_bound, what):
     print(f"{what}: max|d| {d.max().item():.3e} mean|d| {d.mean().item():.3e} on mean|ref| {ref.abs().mean().item():.3f}; worst d / gate {worst:.2f}")
     assert torch.isfinite(out).all() and worst <= 1.0, what
     assert d.mean() <= 2.0 ** -9 * ref.abs().mean() + acc_bound, what        # rounding errors average well below the per-element bound
+
+
+def derived_bound(acc, absacc, K, bias, res, bias2=None, bias2_rows=0):
+    """(ref, B) of tests/mm_gate.py for acc + bias + bias2 + residual: the split-K and tail-split cases are held to |out - ref| <= 2 B as well"""
+    n = acc.shape[-1]
+    ep = mm_gate.Epi(bias=bias, bias2=bias2, bias2_rows=bias2_rows, residual=res.reshape(-1, n))
+    ref, B = mm_gate.epilogue(acc.reshape(-1, n), ep, absacc.reshape(-1, n), K, torch.bfloat16)
+    return ref.reshape(acc.shape), B.reshape(acc.shape)
 
 
 def test_gemm16_geglu_at_level0_shape():
@@ -105,6 +114,7 @@ def test_gemm16_splitk_equals_unsplit_and_fp64(kind, shape):
     from mmgt_amd.packing import pack_conv3x3
     gen = torch.Generator(device=DEV).manual_seed(7)
     ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, generator=gen, device=DEV).float()
+    derived = []                              # (ref, B) of tests/mm_gate.py for the random operands
 
     def run(exact):
         if kind == "conv":
@@ -120,6 +130,9 @@ def test_gemm16_splitk_equals_unsplit_and_fp64(kind, shape):
             f = lambda: hip.conv3x3(x0, wp, b, residual=res, x1=x1)
             xin = x0 if x1 is None else torch.cat([x0, x1], 3)
             ref = F.conv2d(xin.permute(0, 3, 1, 2).double(), w.double(), b.double(), padding=1).permute(0, 2, 3, 1) + res.double()
+            if not exact and not derived:
+                absacc = F.conv2d(xin.permute(0, 3, 1, 2).double().abs(), w.double().abs(), None, padding=1).permute(0, 2, 3, 1)
+                derived.append(derived_bound(ref - b.double() - res.double(), absacc, 9 * (c0 + c1), b, res))
         else:
             M, N, K = shape
             a = ri((M, K), -2, 2).bfloat16() if exact else rnd("sk.a", (M, K))
@@ -128,6 +141,8 @@ def test_gemm16_splitk_equals_unsplit_and_fp64(kind, shape):
             res = ri((M, N), -4, 4).bfloat16() if exact else rnd("sk.rd", (M, N))
             f = lambda: hip.gemm(a, w, b, residual=res)
             ref = a.double() @ w.double().t() + b.double() + res.double()
+            if not exact and not derived:
+                derived.append(derived_bound(a.double() @ w.double().t(), a.double().abs() @ w.double().abs().t(), K, b, res))
         hip.tune("splitk", 1)
         split = f()
         hip.tune("splitk", 0)
@@ -141,6 +156,8 @@ def test_gemm16_splitk_equals_unsplit_and_fp64(kind, shape):
     split, plain, ref = run(exact=False)
     check(split, ref, 4e-5, f"split-K {kind} {shape}")
     check(plain, ref, 4e-5, f"unsplit {kind} {shape}")
+    mm_gate.check(split, *derived[0], f"split-K {kind} {shape}")
+    mm_gate.check(plain, *derived[0], f"unsplit {kind} {shape}")
     again, _, _ = run(exact=False)
     assert torch.equal(split, again), "split-K is not bitwise reproducible"
 
@@ -155,6 +172,7 @@ def test_gemm16_tail_split_equals_one_launch_and_fp64(kind, shape):
     from mmgt_amd.packing import pack_conv3x3
     gen = torch.Generator(device=DEV).manual_seed(11)
     ri = lambda shape, lo, hi: torch.randint(lo, hi + 1, shape, generator=gen, device=DEV).float()
+    derived = []                              # (ref, B) of tests/mm_gate.py for the random operands
 
     def run(exact):
         if kind == "conv":
@@ -172,6 +190,10 @@ def test_gemm16_tail_split_equals_one_launch_and_fp64(kind, shape):
             xin = x0 if x1 is None else torch.cat([x0, x1], 3)
             ref = F.conv2d(xin.permute(0, 3, 1, 2).double(), w.double(), b.double(), padding=1).permute(0, 2, 3, 1) + res.double() + \
                 b2.double().repeat_interleave(nb // 2, 0)[:, None, None, :]
+            if not exact and not derived:
+                absacc = F.conv2d(xin.permute(0, 3, 1, 2).double().abs(), w.double().abs(), None, padding=1).permute(0, 2, 3, 1)
+                acc = ref - b.double() - res.double() - b2.double().repeat_interleave(nb // 2, 0)[:, None, None, :]
+                derived.append(derived_bound(acc, absacc, 9 * (c0 + c1), b, res, b2, (nb // 2) * h * h))
         else:
             M, N, K = shape
             a = ri((M, K), -2, 2).bfloat16() if exact else rnd("ts.a", (M, K))
@@ -180,6 +202,8 @@ def test_gemm16_tail_split_equals_one_launch_and_fp64(kind, shape):
             res = ri((M, N), -4, 4).bfloat16() if exact else rnd("ts.rd", (M, N))
             f = lambda: hip.gemm(a, w, b, residual=res)
             ref = a.double() @ w.double().t() + b.double() + res.double()
+            if not exact and not derived:
+                derived.append(derived_bound(a.double() @ w.double().t(), a.double().abs() @ w.double().abs().t(), K, b, res))
         hip.tune("tailsplit", 1)
         split = f()
         hip.tune("tailsplit", 0)
@@ -194,5 +218,7 @@ def test_gemm16_tail_split_equals_one_launch_and_fp64(kind, shape):
     split, plain, ref = run(exact=False)
     check(split, ref, 4e-5, f"tail split {kind} {shape}")
     check(plain, ref, 4e-5, f"one launch {kind} {shape}")
+    mm_gate.check(split, *derived[0], f"tail split {kind} {shape}")
+    mm_gate.check(plain, *derived[0], f"one launch {kind} {shape}")
     again, _, _ = run(exact=False)
     assert torch.equal(split, again), "the tail split is not bitwise reproducible"
