@@ -482,6 +482,23 @@ int mmgt_png_deflate(const unsigned char* data, const unsigned int* codes, const
  * Nothing outside slots_words / out_bytes is read or written. */
 int mmgt_png_pack(const unsigned int* slots, const long long* slot_off, long long slots_words, const long long* bit_off, unsigned char* out,
                   const long long* out_off, long long out_bytes, int n, int strips, void* stream);
+/* ---- PNG input path (csrc/pngdec.hip, csrc/pngdec_core.h, mmgt_amd/video_in.py): non-interlaced PNG / APNG frames of one geometry.  Every
+ * buffer is a device pointer; the status words are those of csrc/pngdec_core.h (0: fine).  Arguments outside the stated range: non-zero, nothing
+ * launched, mmgt_last_error() says "range".
+ * inflate: stream f is the raw deflate bytes data[offsets[f] .. offsets[f + 1]) (no zlib header or trailer; offsets has n + 1 entries; data and filt
+ * 16-byte aligned, data_bytes a multiple of 16 that covers every stream) -> filt + f * frame_bytes, frame_bytes bytes at most whatever the stream
+ * holds, and status[f].  One 64-thread workgroup per stream; its loop consumes at least one bit per iteration or stops. */
+int mmgt_png_inflate(const unsigned char* data, long long data_bytes, const long long* offsets, unsigned char* filt, int* status, int n,
+                     long long frame_bytes, void* stream);
+/* unfilter: filt (n, H, 1 + ceil(W * bits per pixel / 8)) is reconstructed in place (PNG filter types 0 .. 4, the row above row 0 zeros; a type above
+ * 4 sets status[f] and counts as 0); sums (n, H, 2) = { sum d[i], sum (L - i) d[i] } over each row's L FILTERED bytes, as mmgt_png_filter writes them.
+ * colour type 0 or 3 at depth 1, 2, 4 or 8; 2, 4 or 6 at depth 8; sides 1 .. 16384. */
+int mmgt_png_unfilter(unsigned char* filt, long long* sums, int* status, int n, int H, int W, int colour_type, int depth, void* stream);
+/* expand: reconstructed rows -> out (n, H, W, 3) u8 RGB as PIL's Image.convert("RGB") gives them: grey of 1 / 2 / 4 bits times 255 / 85 / 17, alpha
+ * dropped, colour type 3 looked up in palette (n, 256, 3); an index at or past plte_len[f] sets status[f] (the pixel is black).  palette and plte_len
+ * may be null for the other colour types. */
+int mmgt_png_expand(const unsigned char* filt, const unsigned char* palette, const int* plte_len, unsigned char* out, int* status, int n, int H, int W,
+                    int colour_type, int depth, void* stream);
 /* SMGA key points -> the four frame streams of Stage 2, drawn on the device: kp (frames, 134, 3) fp32 = SMGA's normalised
  * (x, y, score) features.  Replaces data/extract_movment_mask_all.py:319-321 `pose_vid_generator` (denormalize :128-132, mask_leg :66-89,
  * process_keypoints :98-119), src/dwpose/__init__.py:220-283 `DWposeDetector_movment_mask.__call__` with draw_pose / draw_pose_mask_head /

@@ -129,6 +129,9 @@ _SIGS = {
     "mmgt_png_deflate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong,
                                  ctypes.c_longlong, c_void_p]),
     "mmgt_png_pack": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
+    "mmgt_png_inflate": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
+    "mmgt_png_unfilter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_png_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
@@ -1331,6 +1334,87 @@ def png_pack(slots, want_bits, out=None):
         _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, strips,
                                    _stream()), "mmgt_png_pack")
     return out, out_off
+
+
+# ------------------------------------------------------------------------------------------------------------ PNG input (csrc/pngdec.hip)
+
+_PNGDEC_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+
+
+def pngdec_stride(W, colour_type, depth):
+    """Bytes of one filtered scanline: the filter type byte and ceil(W * bits per pixel / 8)."""
+    if colour_type not in _PNGDEC_CHANNELS:
+        raise RuntimeError(f"pngdec: colour type {colour_type} is outside the range (0, 2, 3, 4, 6)")
+    return 1 + (int(W) * _PNGDEC_CHANNELS[colour_type] * int(depth) + 7) // 8
+
+
+def _status_words(status, n, device, what):
+    if status is None:
+        status = torch.empty((n,), device=device, dtype=torch.int32)
+    if status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous() or status.device != device:
+        raise RuntimeError(f"{what}: status must be contiguous int32 ({n},) on {device}")
+    return status
+
+
+def png_inflate(data, offsets, frame_bytes, out=None):
+    """Raw deflate streams data[offsets[f]:offsets[f + 1]] (data uint8, a multiple of 16 bytes; offsets int64 (n + 1,)) -> (filt (n, frame_bytes)
+    uint8, status (n,) int32): include/mmgt_hip.h states the operands.  `out` = (filt, status) to write into, either may be None."""
+    _dev(data, offsets)
+    n = offsets.numel() - 1
+    if (data.dtype != torch.uint8 or data.dim() != 1 or offsets.dtype != torch.int64 or offsets.dim() != 1 or n < 1
+            or not data.is_contiguous() or not offsets.is_contiguous()):
+        raise RuntimeError("png_inflate: expected data uint8 (bytes,) and offsets int64 (n + 1,), n >= 1, both contiguous")
+    filt, status = out if out is not None else (None, None)
+    if filt is None:
+        filt = torch.empty((n, int(frame_bytes)), device=data.device, dtype=torch.uint8)
+    if filt.dtype != torch.uint8 or tuple(filt.shape) != (n, int(frame_bytes)) or not filt.is_contiguous() or filt.device != data.device:
+        raise RuntimeError(f"png_inflate: filt must be contiguous uint8 ({n}, {int(frame_bytes)}) on {data.device}")
+    status = _status_words(status, n, data.device, "png_inflate")
+    _check(lib().mmgt_png_inflate(_ptr(data), data.numel(), _ptr(offsets), _ptr(filt), _ptr(status), n, int(frame_bytes), _stream()), "mmgt_png_inflate")
+    return filt, status
+
+
+def png_unfilter(filt, H, W, colour_type, depth, out=None):
+    """Filtered scanlines (n, H * stride) uint8, reconstructed IN PLACE -> (sums (n, H, 2) int64, status (n,) int32): the two sums of which the
+    host makes each row's Adler-32, over the bytes as they were (see mmgt_png_unfilter).  `out` = (sums, status) to write into, either may be None."""
+    _dev(filt)
+    H, W = int(H), int(W)
+    stride = pngdec_stride(W, colour_type, depth)
+    n = filt.shape[0]
+    if filt.dtype != torch.uint8 or tuple(filt.shape) != (n, H * stride) or not filt.is_contiguous() or n < 1:
+        raise RuntimeError(f"png_unfilter: expected filt uint8 (n, {H * stride}), contiguous")
+    sums, status = out if out is not None else (None, None)
+    if sums is None:
+        sums = torch.empty((n, H, 2), device=filt.device, dtype=torch.int64)
+    if sums.dtype != torch.int64 or tuple(sums.shape) != (n, H, 2) or not sums.is_contiguous() or sums.device != filt.device:
+        raise RuntimeError(f"png_unfilter: sums must be contiguous int64 ({n}, {H}, 2) on {filt.device}")
+    status = _status_words(status, n, filt.device, "png_unfilter")
+    _check(lib().mmgt_png_unfilter(_ptr(filt), _ptr(sums), _ptr(status), n, H, W, int(colour_type), int(depth), _stream()), "mmgt_png_unfilter")
+    return sums, status
+
+
+def png_expand(filt, H, W, colour_type, depth, palette=None, plte_len=None, out=None):
+    """Reconstructed scanlines (n, H * stride) -> (pixels (n, H, W, 3) uint8 RGB, status (n,) int32); colour type 3 takes palette (n, 256, 3) uint8 and
+    plte_len (n,) int32.  `out` = (pixels, status) to write into, either may be None."""
+    _dev(filt, palette, plte_len)
+    H, W = int(H), int(W)
+    stride = pngdec_stride(W, colour_type, depth)
+    n = filt.shape[0]
+    if filt.dtype != torch.uint8 or tuple(filt.shape) != (n, H * stride) or not filt.is_contiguous() or n < 1:
+        raise RuntimeError(f"png_expand: expected filt uint8 (n, {H * stride}), contiguous")
+    if int(colour_type) == 3 and (palette is None or plte_len is None or palette.dtype != torch.uint8 or tuple(palette.shape) != (n, 256, 3)
+                                  or plte_len.dtype != torch.int32 or tuple(plte_len.shape) != (n,) or not palette.is_contiguous()
+                                  or not plte_len.is_contiguous()):
+        raise RuntimeError(f"png_expand: colour type 3 needs palette uint8 ({n}, 256, 3) and plte_len int32 ({n},), contiguous")
+    pixels, status = out if out is not None else (None, None)
+    if pixels is None:
+        pixels = torch.empty((n, H, W, 3), device=filt.device, dtype=torch.uint8)
+    if pixels.dtype != torch.uint8 or tuple(pixels.shape) != (n, H, W, 3) or not pixels.is_contiguous() or pixels.device != filt.device:
+        raise RuntimeError(f"png_expand: out must be contiguous uint8 ({n}, {H}, {W}, 3) on {filt.device}")
+    status = _status_words(status, n, filt.device, "png_expand")
+    _check(lib().mmgt_png_expand(_ptr(filt), _ptr(palette), _ptr(plte_len), _ptr(pixels), _ptr(status), n, H, W, int(colour_type), int(depth),
+                                 _stream()), "mmgt_png_expand")
+    return pixels, status
 
 
 def dwpose_draw(kp, H=512, W=512):

@@ -4,7 +4,12 @@
                        host, with a ValueError naming the feature, everything the kernels do not decode
   decode_jpeg_frames   a batch of equally sized JPEG files -> (n, H, W, 3) uint8 RGB on the device: Huffman decode, dequantiser + inverse DCT,
                        chroma up-sampling and colour conversion run in csrc/jpegdec.hip, bit for bit libjpeg's (libjpeg-turbo's) default decode
-  read_frames_device   a Motion-JPEG .avi or a directory of .jpg frames -> the same tensor; anything else raises (inputs.read_frames is the host route)
+  parse_png            the chunks of one PNG / APNG file -> PngHeader (geometry, palette, every frame's raw deflate bytes and expected Adler-32);
+                       refuses on the host, with a ValueError naming the feature, everything the kernels do not decode
+  decode_png_frames    PNG / APNG files of one geometry -> (n, H, W, 3) uint8 RGB on the device: inflate, scanline reconstruction and expansion run
+                       in csrc/pngdec.hip, byte for byte PIL's Image.open(f).convert("RGB")
+  read_frames_device   a Motion-JPEG .avi, a directory of .jpg frames, a directory of .png frames or one .png / .apng file (animated or not) -> the
+                       same tensor; anything else raises (inputs.read_frames is the host route)
 """
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -12,7 +17,7 @@ from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .video_out import _AC_BITS, _AC_VALS, _DC_BITS
+from .video_out import _AC_BITS, _AC_VALS, _DC_BITS, _ADLER, PNG_MAX_SIDE, _PNG_SIG
 
 # T.81 figure A.6: zigzag position -> natural index
 ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
@@ -297,26 +302,276 @@ def decode_jpeg_frames(jpegs, device="cuda", out=None):
     return hip.jpegdec_color(planes, H, W, ncomp, hs, vs, out=out)
 
 
+# ---------------------------------------------------------------------------------------------------------------- PNG / APNG
+
+PNGDEC_SCRATCH_BYTES = 256 << 20    # decode_png_frames holds at most this much filtered rows and row sums per set of launches
+
+# csrc/pngdec_core.h's status words
+PNG_STATUS_TEXT = {1: "an over-subscribed Huffman code", 2: "an incomplete Huffman code", 3: "an invalid symbol", 4: "a distance beyond the bytes produced",
+                   5: "a stored block whose LEN and NLEN do not match", 6: "data exhausted before the final block's end",
+                   7: "more image data than the frame holds (output too long)", 8: "less image data than the frame holds (output too short)",
+                   9: "a bad code-length repeat", 10: "more than 286 literal/length or 30 distance codes", 11: "a code without an end-of-block symbol",
+                   12: "block type 3", 13: "a stream descriptor outside the batch", 14: "a scanline filter type above 4",
+                   15: "a palette index beyond PLTE"}
+
+_PNG_CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+
+
+@dataclass
+class PngHeader:
+    width: int
+    height: int
+    colour_type: int                             # 0 grey, 2 RGB, 3 palette, 4 grey + alpha, 6 RGBA
+    bit_depth: int
+    palette: Optional[np.ndarray]                # (entries, 3) uint8 for colour type 3
+    streams: List[bytes] = field(default_factory=list)       # per frame: the raw deflate bytes (IDAT / fdAT payloads joined, zlib header and trailer cut)
+    adlers: List[int] = field(default_factory=list)          # per frame: the zlib trailer, the Adler-32 its filtered bytes must have
+    animated: bool = False                       # acTL present: the frames are the animation's
+    plays: int = 0
+
+    @property
+    def geometry(self):
+        return self.height, self.width, self.colour_type, self.bit_depth
+
+    @property
+    def stride(self):
+        """Bytes of one filtered scanline: the filter type and ceil(W * bits per pixel / 8)."""
+        return 1 + (self.width * _PNG_CHANNELS[self.colour_type] * self.bit_depth + 7) // 8
+
+
+def _zlib_range(stream: bytes, what: str):
+    """One frame's zlib stream -> (raw deflate bytes, expected Adler-32)."""
+    if len(stream) < 6:
+        raise ValueError(f"parse_png: bad zlib header ({what} holds {len(stream)} bytes: no room for header and trailer)")
+    cmf, flg = stream[0], stream[1]
+    if cmf & 15 != 8 or cmf >> 4 > 7 or (cmf << 8 | flg) % 31 or flg & 0x20:
+        raise ValueError(f"parse_png: bad zlib header {cmf:#04x} {flg:#04x} in {what} (CM 8, CINFO <= 7, no FDICT, FCHECK)")
+    return stream[2:-4], int.from_bytes(stream[-4:], "big")
+
+
+def parse_png(data) -> PngHeader:
+    """One PNG / APNG file (bytes) -> PngHeader.  Every chunk's CRC-32 is verified.  ValueError for everything outside the decoder's scope: bit depth
+    16, Adam7 interlace, APNG frames that are not full size at (0, 0) or that blend OVER where the image has transparency, a default image outside
+    the animation, missing IHDR / PLTE / IDAT / IEND, a bad CRC, a bad zlib header, an unknown critical chunk."""
+    import zlib
+    data = bytes(data)
+    if data[:8] != _PNG_SIG:
+        raise ValueError("parse_png: not a PNG file (bad signature)")
+    pos, n = 8, len(data)
+    ihdr = palette = actl = None
+    idat, frames, ctl, seq, trns, ended = [], [], [], 0, False, False          # frames: [fcTL or None, [payloads]]
+    while pos < n:
+        if pos + 12 > n:
+            raise ValueError(f"parse_png: a chunk header at byte {pos} runs past the end of the file" + ("" if ihdr else " (missing IHDR)"))
+        length, kind = int.from_bytes(data[pos:pos + 4], "big"), data[pos + 4:pos + 8]
+        if pos + 12 + length > n:
+            raise ValueError(f"parse_png: chunk {kind!r} at byte {pos} runs past the end of the file (missing IEND)")
+        body = data[pos + 8:pos + 8 + length]
+        if zlib.crc32(data[pos + 4:pos + 8 + length]) != int.from_bytes(data[pos + 8 + length:pos + 12 + length], "big"):
+            raise ValueError(f"parse_png: bad CRC in chunk {kind!r} at byte {pos}")
+        pos += 12 + length
+        if ihdr is None and kind != b"IHDR":
+            raise ValueError(f"parse_png: missing IHDR (the first chunk is {kind!r})")
+        if kind == b"IHDR":
+            if ihdr is not None or length != 13:
+                raise ValueError("parse_png: bad IHDR chunk")
+            ihdr = body
+        elif kind == b"PLTE":
+            if length % 3 or not 3 <= length <= 768 or idat:
+                raise ValueError("parse_png: bad PLTE chunk")
+            palette = np.frombuffer(body, np.uint8).reshape(-1, 3).copy()
+        elif kind == b"IDAT":
+            idat.append(body)
+        elif kind == b"IEND":
+            ended = True
+            break
+        elif kind == b"tRNS":
+            trns = True                                                           # ignored, as Image.convert("RGB") ignores it
+        elif kind == b"acTL" and length == 8 and not idat:
+            actl = (int.from_bytes(body[:4], "big"), int.from_bytes(body[4:], "big"))
+        elif kind == b"fcTL" and actl is not None:
+            if length != 26 or int.from_bytes(body[:4], "big") != seq:
+                raise ValueError("parse_png: bad fcTL chunk (its length or sequence number)")
+            seq += 1
+            if not frames and idat:
+                raise ValueError("parse_png: an APNG whose default image is not its first frame is not decoded")
+            frames.append([body, idat if not frames else []])
+        elif kind == b"fdAT" and actl is not None:
+            if length < 4 or int.from_bytes(body[:4], "big") != seq or not frames or frames[-1][1] is idat:
+                raise ValueError("parse_png: bad fdAT chunk (its sequence number or place)")
+            seq += 1
+            frames[-1][1].append(body[4:])
+        elif not kind[0] & 0x20:
+            raise ValueError(f"parse_png: unknown critical chunk {kind!r}")
+        # every other ancillary chunk: skipped
+    if ihdr is None:
+        raise ValueError("parse_png: missing IHDR")
+    if not ended:
+        raise ValueError("parse_png: missing IEND")
+    W, H = int.from_bytes(ihdr[:4], "big"), int.from_bytes(ihdr[4:8], "big")
+    depth, ct, comp, filt, lace = ihdr[8:13]
+    if lace == 1:
+        raise ValueError("parse_png: Adam7 interlace is not decoded")
+    if depth == 16 and ct in _PNG_CHANNELS:
+        raise ValueError("parse_png: bit depth 16 is not decoded (1, 2, 4 or 8 bits)")
+    if ct not in _PNG_CHANNELS or depth not in ((1, 2, 4, 8) if ct in (0, 3) else (8,)) or comp or filt or lace:
+        raise ValueError(f"parse_png: bad IHDR (colour type {ct}, bit depth {depth}, compression {comp}, filter {filt}, interlace {lace})")
+    if not (1 <= W <= PNG_MAX_SIDE and 1 <= H <= PNG_MAX_SIDE):
+        raise ValueError(f"parse_png: a frame is 1 .. {PNG_MAX_SIDE} pixels a side, got {W} x {H}")
+    if ct == 3 and palette is None:
+        raise ValueError("parse_png: a palette image without PLTE")
+    if not idat:
+        raise ValueError("parse_png: missing IDAT")
+    h = PngHeader(W, H, ct, depth, palette if ct == 3 else None)
+    if actl is None:
+        frames = [[None, idat]]
+    else:
+        h.animated, h.plays = True, actl[1]
+        if not frames or frames[0][1] is not idat:
+            raise ValueError("parse_png: an APNG whose default image is not its first frame is not decoded")
+        if len(frames) != actl[0]:
+            raise ValueError(f"parse_png: acTL announces {actl[0]} frames, the file holds {len(frames)}")
+    for k, (fctl, parts) in enumerate(frames):
+        if fctl is not None:
+            fw, fh, fx, fy = (int.from_bytes(fctl[4 + 4 * i:8 + 4 * i], "big") for i in range(4))
+            dispose, blend = fctl[24], fctl[25]
+            if (fw, fh, fx, fy) != (W, H, 0, 0):
+                raise ValueError(f"parse_png: APNG sub-rectangle frames are not decoded (frame {k} is {fw} x {fh} at ({fx}, {fy}) of {W} x {H})")
+            if dispose > 2 or blend > 1:
+                raise ValueError(f"parse_png: bad fcTL chunk (dispose {dispose}, blend {blend})")
+            if blend == 1 and k > 0 and (ct in (4, 6) or trns):
+                raise ValueError(f"parse_png: APNG blend OVER on an image with transparency is not decoded (frame {k}): the frame shown is composed "
+                                 "from the one before")
+        if not parts:
+            raise ValueError(f"parse_png: missing IDAT (frame {k} has no image data)")
+        raw, adler = _zlib_range(b"".join(parts), f"frame {k}" if h.animated else "IDAT")
+        h.streams.append(raw)
+        h.adlers.append(adler)
+    return h
+
+
+def png_batch_operands(pngs, headers=None):
+    """Host-side operands of one decode call: (headers, geometry (H, W, colour type, depth), data uint8 (bytes,) padded to a multiple of 16, offsets int64
+    (n + 1,), adlers (n,), palette uint8 (n, 256, 3) or None, plte_len int32 (n,)).  Every frame of every file counts: n = all frames in order."""
+    headers = [parse_png(b) for b in pngs] if headers is None else headers
+    if not headers:
+        raise ValueError("decode_png_frames: no frames")
+    g0 = headers[0]
+    for k, h in enumerate(headers):
+        if h.geometry != g0.geometry:
+            raise ValueError(f"decode_png_frames: file {k} is {h.width} x {h.height}, colour type {h.colour_type} at {h.bit_depth} bits; file 0 is "
+                             f"{g0.width} x {g0.height}, colour type {g0.colour_type} at {g0.bit_depth} bits: one call decodes one geometry")
+    streams = [s for h in headers for s in h.streams]
+    adlers = np.asarray([a for h in headers for a in h.adlers], np.int64)
+    offsets = np.zeros(len(streams) + 1, np.int64)
+    np.cumsum([len(s) for s in streams], out=offsets[1:])
+    blob = b"".join(streams)
+    data = np.frombuffer(blob + bytes(16 + (-len(blob)) % 16), np.uint8)
+    palette = plte_len = None
+    if g0.colour_type == 3:
+        palette = np.zeros((len(streams), 256, 3), np.uint8)
+        plte_len = np.zeros(len(streams), np.int32)
+        f = 0
+        for h in headers:
+            for _ in h.streams:
+                palette[f, :len(h.palette)] = h.palette
+                plte_len[f] = len(h.palette)
+                f += 1
+    return headers, g0.geometry, data, offsets, adlers, palette, plte_len
+
+
+def adler32_of_row_sums(sums, stride) -> np.ndarray:
+    """sums (n, H, 2) = per filtered scanline { sum d[i], sum (stride - i) d[i] } -> (n,) the Adler-32 of each frame's H * stride bytes: what folding
+    video_out.adler32_combine over the rows' own Adler-32s gives, in one numpy expression."""
+    s = np.asarray(sums, np.int64) % _ADLER
+    n, H, _ = s.shape
+    after = (np.arange(H - 1, -1, -1, dtype=np.int64) * (stride % _ADLER)) % _ADLER           # bytes behind each row, mod 65521
+    a = (1 + s[:, :, 0].sum(axis=1)) % _ADLER
+    b = ((H * stride) % _ADLER + ((s[:, :, 1] + after[None] * s[:, :, 0]) % _ADLER).sum(axis=1)) % _ADLER
+    return b << 16 | a
+
+
+def decode_png_frames(pngs, device="cuda", out=None):
+    """PNG / APNG files (bytes each) of one size, colour type and bit depth (palettes may differ per file) -> (n, H, W, 3) uint8 RGB on `device`,
+    contiguous, n = all frames of all files in order: byte for byte Image.open(f).convert("RGB") (grey of 1 / 2 / 4 bits scaled to 0 .. 255, alpha
+    dropped, tRNS ignored, palette entries copied).  `out`: a tensor of that shape to write into.  Out-of-scope files raise ValueError before
+    anything is launched.  Image data that does not inflate, a filter type above 4, an Adler-32 that differs from the stream's trailer or a palette
+    index beyond PLTE raise RuntimeError naming the first bad frame (the status words and row sums are read once per call); no pixels are returned."""
+    return _decode_png_operands(png_batch_operands(pngs), device, out)
+
+
+def _decode_png_operands(operands, device, out=None):
+    import torch
+    from . import hip
+    headers, (H, W, ct, depth), data, offsets, adlers, palette, plte_len = operands
+    n, stride = len(adlers), headers[0].stride
+    dev = torch.device(device)
+    if out is None:
+        out = torch.empty((n, H, W, 3), device=dev, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError(f"decode_png_frames: out must be contiguous uint8 ({n}, {H}, {W}, 3) on the device")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_data, d_off = up(data.copy()), up(offsets)
+    d_pal, d_len = (up(palette), up(plte_len)) if ct == 3 else (None, None)
+    status = torch.empty((3, n), device=dev, dtype=torch.int32)
+    sums = torch.empty((n, H, 2), device=dev, dtype=torch.int64)
+    per_call = max(1, PNGDEC_SCRATCH_BYTES // (H * stride + 16 * H))
+    for f0 in range(0, n, per_call):
+        f1 = min(n, f0 + per_call)
+        filt, _ = hip.png_inflate(d_data, d_off[f0:f1 + 1], H * stride, out=(None, status[0, f0:f1]))
+        hip.png_unfilter(filt, H, W, ct, depth, out=(sums[f0:f1], status[1, f0:f1]))
+        hip.png_expand(filt, H, W, ct, depth, d_pal[f0:f1] if ct == 3 else None, d_len[f0:f1] if ct == 3 else None, out=(out[f0:f1], status[2, f0:f1]))
+    st = status.cpu().numpy()                                                  # the one read of the status words (it also orders the launches)
+    for stage, name in ((0, "image data"), (1, "scanlines")):
+        bad = np.flatnonzero(st[stage])
+        if bad.size:
+            f = int(bad[0])
+            raise RuntimeError(f"decode_png_frames: frame {f}, {name}: {PNG_STATUS_TEXT.get(int(st[stage, f]), f'status {int(st[stage, f])}')}")
+    got = adler32_of_row_sums(sums.cpu().numpy(), stride)
+    bad = np.flatnonzero(got != adlers)
+    if bad.size:
+        f = int(bad[0])
+        raise RuntimeError(f"decode_png_frames: frame {f}: the image data's Adler-32 is {int(got[f]):#010x}, the stream's trailer says {int(adlers[f]):#010x}")
+    bad = np.flatnonzero(st[2])
+    if bad.size:
+        f = int(bad[0])
+        raise RuntimeError(f"decode_png_frames: frame {f}, pixels: {PNG_STATUS_TEXT.get(int(st[2, f]), f'status {int(st[2, f])}')}")
+    return out
+
+
 def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
     """(L, H, W, 3) uint8 RGB frames of `path` on `device`, decoded there: a Motion-JPEG .avi (what video_out.write_avi writes, or any stock
-    tool's `-c:v mjpeg`) or a directory whose images are all .jpg / .jpeg (sorted by name).  Everything else raises: inputs.read_frames is the
-    host route, and the caller chooses it."""
+    tool's `-c:v mjpeg`), a directory whose images are all .jpg / .jpeg or all .png (sorted by name; a .png file gives its first frame), or one
+    .png / .apng file, animated or not (what video_out.write_apng / write_png write).  Everything else raises: inputs.read_frames is the host route,
+    and the caller chooses it."""
     from .inputs import IMAGE_SUFFIXES, mjpeg_avi_frames
     p = Path(path)
     if not p.exists():
         raise FileNotFoundError(f"read_frames_device: {p} does not exist")
     if p.is_dir():
         files = sorted(f for f in p.iterdir() if f.is_file() and f.suffix.lower() in IMAGE_SUFFIXES)
+        if {f.suffix.lower() for f in files} == {".png"}:
+            heads = [parse_png(f.read_bytes()) for f in (files if limit is None else files[:limit])]
+            for h in heads:                                                   # a file of a directory is one frame, as for inputs.read_frames
+                h.streams, h.adlers = h.streams[:1], h.adlers[:1]
+            return _decode_png_operands(png_batch_operands(None, heads), device)
         other = [f.name for f in files if f.suffix.lower() not in (".jpg", ".jpeg")]
         if not files or other:
-            raise RuntimeError(f"read_frames_device: {p} must hold .jpg / .jpeg frames only ({'found ' + other[0] if other else 'no images'}); "
-                               "use inputs.read_frames for other inputs")
+            raise RuntimeError(f"read_frames_device: {p} must hold .jpg / .jpeg frames only, or .png frames only "
+                               f"({'found ' + other[0] if other else 'no images'}); use inputs.read_frames for other inputs")
         jpegs = [f.read_bytes() for f in (files if limit is None else files[:limit])]
+    elif p.suffix.lower() in (".png", ".apng"):
+        h = parse_png(p.read_bytes())
+        if limit is not None:
+            h.streams, h.adlers = h.streams[:limit], h.adlers[:limit]
+        if not h.streams:
+            raise RuntimeError(f"read_frames_device: no frames in {p}")
+        return _decode_png_operands(png_batch_operands(None, [h]), device)
     else:
         jpegs = mjpeg_avi_frames(p, limit) if p.suffix.lower() == ".avi" else None
         if jpegs is None:
-            raise RuntimeError(f"read_frames_device: {p.name} is neither a Motion-JPEG .avi nor a directory of .jpg frames; "
-                               "use inputs.read_frames for other inputs")
+            raise RuntimeError(f"read_frames_device: {p.name} is neither a Motion-JPEG .avi, a .png / .apng file nor a directory of .jpg or .png "
+                               "frames; use inputs.read_frames for other inputs")
     if not jpegs:
         raise RuntimeError(f"read_frames_device: no frames in {p}")
     return decode_jpeg_frames(jpegs, device)

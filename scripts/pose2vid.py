@@ -62,8 +62,8 @@ def parse_args():
                         "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
     p.add_argument("--decoder", default="pil", choices=["pil", "device"],
                    help="how --pose_path and the mask paths are read: pil = on the host (any input read_frames takes); device = Motion-JPEG "
-                        ".avi or a directory of .jpg frames, decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
-                        "resized on the device too (a baseline .jpg is also decoded there)")
+                        ".avi, a directory of .jpg or of .png frames, or a .png / .apng file, decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
+                        "resized on the device too (a baseline .jpg or a .png is also decoded there)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -148,8 +148,8 @@ def build_from_checkpoints(cfg_path, num_c, dev, dtype):
 
 
 def load_inputs(a, dev):
-    """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG on
-    the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
+    """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG
+    and PNG / APNG on the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
     from mmgt_amd import inputs
     device = getattr(a, "decoder", "pil") == "device"
     if device:
@@ -177,17 +177,18 @@ def load_inputs(a, dev):
 
 def load_ref_image(a, dev):
     """The reference image as the pipeline takes it: a PIL image, or with --decoder device a uint8 (h, w, 3) tensor on the device -- a baseline
-    .jpg is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
+    .jpg or a .png is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
     from PIL import Image
     if getattr(a, "decoder", "pil") != "device":
         return Image.open(a.image_path).convert("RGB")
-    if os.path.splitext(a.image_path)[1].lower() in (".jpg", ".jpeg"):
-        from mmgt_amd.video_in import decode_jpeg_frames
+    suffix = os.path.splitext(a.image_path)[1].lower()
+    if suffix in (".jpg", ".jpeg", ".png"):
+        from mmgt_amd.video_in import decode_jpeg_frames, decode_png_frames
         with open(a.image_path, "rb") as fh:
             data = fh.read()
         try:
-            return decode_jpeg_frames([data], dev)[0]
-        except ValueError as e:                                  # outside the device decoder's scope (progressive, CMYK, ...): parse_jpeg says why
+            return (decode_png_frames if suffix == ".png" else decode_jpeg_frames)([data], dev)[0]
+        except ValueError as e:                                  # outside the device decoders' scope (progressive, CMYK, 16 bit, interlace, ...): the parser says why
             print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
     import numpy as np
     return torch.from_numpy(np.asarray(Image.open(a.image_path).convert("RGB")).copy()).to(dev)
