@@ -499,6 +499,23 @@ int mmgt_png_unfilter(unsigned char* filt, long long* sums, int* status, int n, 
  * may be null for the other colour types. */
 int mmgt_png_expand(const unsigned char* filt, const unsigned char* palette, const int* plte_len, unsigned char* out, int* status, int n, int H, int W,
                     int colour_type, int depth, void* stream);
+/* ---- GIF input path (csrc/gifdec.hip, csrc/gifdec_core.h, mmgt_amd/video_in.py): a chunk of n consecutive frames of one GIF file.  Every
+ * buffer is a device pointer; the status words are those of csrc/gifdec_core.h (0: fine).  tab (n, 16) long long is one row per frame (gifdec_core.h:
+ * GD_X .. GD_FILL): rectangle, index-buffer offset, code-stream byte range in data, minimum code size, interlace flag, transparent index or -1, what the
+ * frame leaves pending (0 nothing, 2 a colour, 3 the canvas before it drew), that colour, first-frame flag and first-frame fill colour.  Arguments
+ * outside the stated range: non-zero, nothing launched, mmgt_last_error() says "range".
+ * unlzw: frame f's LZW codes data[tab[f].begin .. tab[f].end) (sub-block framing removed; data_bytes a positive multiple of 16 that covers every
+ * stream; 1 <= n <= 65535) -> its W * H palette indices in stream order at idx + tab[f].idx, never more, and status[f].  A row that names bytes
+ * outside data_bytes / idx_bytes, a rectangle outside 16384 x 16384 or a code size outside 2 .. 8 gives status 4 and touches nothing.  One 64-thread
+ * workgroup per frame; every round of its loop consumes at least one code or stops. */
+int mmgt_gif_unlzw(const unsigned char* data, long long data_bytes, const long long* tab, unsigned char* idx, long long idx_bytes, int* status, int n,
+                   void* stream);
+/* compose: the chunk's frames drawn in order on the H x W canvas (sides 1 .. 16384, 1 <= n <= 65535) through palette (n, 256, 3) -> out (n, H, W, 3) u8
+ * RGB, as PIL's ImageSequence.Iterator + convert("RGB") gives them.  carry (2, H, W, 3) holds the canvas and what it becomes before the next frame
+ * draws: read unless tab[0] is the file's first frame, written at the end, so that a file may be decoded in chunks.  A row whose rectangle leaves
+ * the canvas or whose indices leave idx_bytes draws nothing. */
+int mmgt_gif_compose(const long long* tab, const unsigned char* idx, long long idx_bytes, const unsigned char* palette, unsigned char* carry,
+                     unsigned char* out, int n, int H, int W, void* stream);
 /* SMGA key points -> the four frame streams of Stage 2, drawn on the device: kp (frames, 134, 3) fp32 = SMGA's normalised
  * (x, y, score) features.  Replaces data/extract_movment_mask_all.py:319-321 `pose_vid_generator` (denormalize :128-132, mask_leg :66-89,
  * process_keypoints :98-119), src/dwpose/__init__.py:220-283 `DWposeDetector_movment_mask.__call__` with draw_pose / draw_pose_mask_head /

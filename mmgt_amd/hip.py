@@ -132,6 +132,8 @@ _SIGS = {
     "mmgt_png_inflate": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "mmgt_png_unfilter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_png_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_gif_unlzw": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
+    "mmgt_gif_compose": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
@@ -1415,6 +1417,54 @@ def png_expand(filt, H, W, colour_type, depth, palette=None, plte_len=None, out=
     _check(lib().mmgt_png_expand(_ptr(filt), _ptr(palette), _ptr(plte_len), _ptr(pixels), _ptr(status), n, H, W, int(colour_type), int(depth),
                                  _stream()), "mmgt_png_expand")
     return pixels, status
+
+
+# ------------------------------------------------------------------------------------------------------------ GIF input (csrc/gifdec.hip)
+
+GIFDEC_TAB = 16                     # long long words per frame row (csrc/gifdec_core.h: GD_TAB)
+
+
+def _gif_tab(tab, what):
+    if tab.dtype != torch.int64 or tab.dim() != 2 or tab.shape[1] != GIFDEC_TAB or tab.shape[0] < 1 or not tab.is_contiguous():
+        raise RuntimeError(f"{what}: expected tab int64 (n, {GIFDEC_TAB}), n >= 1, contiguous")
+    return tab.shape[0]
+
+
+def gif_unlzw(data, tab, idx_bytes, out=None):
+    """The LZW code streams of n frames (data uint8, a multiple of 16 bytes; tab int64 (n, 16), one row per frame: include/mmgt_hip.h) -> (idx
+    (idx_bytes,) uint8: every frame's palette indices in stream order at its row's offset, status (n,) int32).  `out` = (idx, status) to write into,
+    either may be None."""
+    _dev(data, tab)
+    n = _gif_tab(tab, "gif_unlzw")
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise RuntimeError("gif_unlzw: expected data uint8 (bytes,), contiguous")
+    idx, status = out if out is not None else (None, None)
+    if idx is None:
+        idx = torch.empty((int(idx_bytes),), device=data.device, dtype=torch.uint8)
+    if idx.dtype != torch.uint8 or tuple(idx.shape) != (int(idx_bytes),) or not idx.is_contiguous() or idx.device != data.device:
+        raise RuntimeError(f"gif_unlzw: idx must be contiguous uint8 ({int(idx_bytes)},) on {data.device}")
+    status = _status_words(status, n, data.device, "gif_unlzw")
+    _check(lib().mmgt_gif_unlzw(_ptr(data), data.numel(), _ptr(tab), _ptr(idx), idx.numel(), _ptr(status), n, _stream()), "mmgt_gif_unlzw")
+    return idx, status
+
+
+def gif_compose(tab, idx, palette, carry, H, W, out=None):
+    """The chunk's frames composed on the H x W canvas: tab int64 (n, 16), idx uint8 (bytes,) as gif_unlzw wrote it, palette uint8 (n, 256, 3), carry
+    uint8 (2, H, W, 3) (read unless tab[0] is the file's first frame, written at the end) -> (n, H, W, 3) uint8 RGB.  `out`: a tensor to write into."""
+    _dev(tab, idx, palette, carry)
+    n, H, W = _gif_tab(tab, "gif_compose"), int(H), int(W)
+    if idx.dtype != torch.uint8 or idx.dim() != 1 or not idx.is_contiguous():
+        raise RuntimeError("gif_compose: expected idx uint8 (bytes,), contiguous")
+    if palette.dtype != torch.uint8 or tuple(palette.shape) != (n, 256, 3) or not palette.is_contiguous():
+        raise RuntimeError(f"gif_compose: expected palette uint8 ({n}, 256, 3), contiguous")
+    if carry.dtype != torch.uint8 or tuple(carry.shape) != (2, H, W, 3) or not carry.is_contiguous():
+        raise RuntimeError(f"gif_compose: expected carry uint8 (2, {H}, {W}, 3), contiguous")
+    if out is None:
+        out = torch.empty((n, H, W, 3), device=idx.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous() or out.device != idx.device:
+        raise RuntimeError(f"gif_compose: out must be contiguous uint8 ({n}, {H}, {W}, 3) on {idx.device}")
+    _check(lib().mmgt_gif_compose(_ptr(tab), _ptr(idx), idx.numel(), _ptr(palette), _ptr(carry), _ptr(out), n, H, W, _stream()), "mmgt_gif_compose")
+    return out
 
 
 def dwpose_draw(kp, H=512, W=512):

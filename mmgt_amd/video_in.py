@@ -8,8 +8,13 @@
                        refuses on the host, with a ValueError naming the feature, everything the kernels do not decode
   decode_png_frames    PNG / APNG files of one geometry -> (n, H, W, 3) uint8 RGB on the device: inflate, scanline reconstruction and expansion run
                        in csrc/pngdec.hip, byte for byte PIL's Image.open(f).convert("RGB")
-  read_frames_device   a Motion-JPEG .avi, a directory of .jpg frames, a directory of .png frames or one .png / .apng file (animated or not) -> the
-                       same tensor; anything else raises (inputs.read_frames is the host route)
+  parse_gif            the blocks of one GIF87a / GIF89a file -> GifHeader (screen, and per frame the rectangle, flags, colour table and LZW bytes with
+                       the sub-block framing removed); refuses on the host, with a ValueError naming the cause, what the kernels do not decode
+                       
+  decode_gif_frames    one GIF file -> (n, H, W, 3) uint8 RGB on the device: un-LZW, de-interlace and PIL's frame composition (sub-rectangles, local
+                       palettes, transparency, the four disposals) run in csrc/gifdec.hip, byte for byte ImageSequence.Iterator + convert("RGB")
+  read_frames_device   a Motion-JPEG .avi, a directory of .jpg frames, a directory of .png frames, one .png / .apng file (animated or not) or one
+                       .gif file -> the same tensor; anything else raises (inputs.read_frames is the host route)
 """
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -539,11 +544,215 @@ def _decode_png_operands(operands, device, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------------- GIF
+
+GIFDEC_SCRATCH_BYTES = 256 << 20    # decode_gif_frames holds at most this many palette indices per set of launches (one frame at least)
+GIF_MAX_SIDE = 16384
+
+# csrc/gifdec_core.h's status words
+GIF_STATUS_TEXT = {1: "a code above the next free one", 2: "a first code after a clear that is not a literal",
+                   3: "the image data ends before the frame's pixels are complete", 4: "a frame descriptor outside the batch"}
+
+# csrc/gifdec_core.h's table row (checked against the binding's GIFDEC_TAB on every call)
+_GD_X, _GD_Y, _GD_W, _GD_H, _GD_IDX, _GD_BEGIN, _GD_END, _GD_MCS, _GD_LACE, _GD_TRANS, _GD_MODE, _GD_COLOUR, _GD_FIRST, _GD_FILL = range(14)
+GIF_TAB = 16
+
+
+@dataclass
+class GifFrame:
+    x: int
+    y: int
+    width: int
+    height: int
+    interlace: bool
+    min_code_size: int                           # 2 .. 8
+    transparent: Optional[int]                   # the graphic control extension's transparent index, or None
+    disposal: int                                # the graphic control extension's disposal bits as they stand in the file (0 without one)
+    palette: np.ndarray                          # (256, 3) uint8: the local colour table, else the global one, zero padded
+    colours: int                                 # entries of that table
+    lzw: bytes                                   # the code stream, sub-block framing removed
+
+
+@dataclass
+class GifHeader:
+    width: int                                   # the logical screen
+    height: int
+    background: int                              # the screen descriptor's background index; 0 in a file without a global colour table
+    frames: List[GifFrame] = field(default_factory=list)
+
+
+def parse_gif(data) -> GifHeader:
+    """One GIF87a / GIF89a file (bytes) -> GifHeader.  Graphic control extensions are read, every other extension is skipped; bytes that open no
+    block are skipped as PIL skips them, and a file that ends without a trailer after its last complete image is taken as PIL takes it.  ValueError
+    for everything outside the decoder's scope: a bad signature, a block or sub-block that runs past the end of the file, a missing trailer before
+    any image, a frame without a colour table, a frame rectangle that is empty or leaves the logical screen, a minimum code size outside 2 .. 8, a
+    screen outside 1 .. 16384 a side, no frames."""
+    data = bytes(data)
+    n = len(data)
+    if data[:6] not in (b"GIF87a", b"GIF89a"):
+        raise ValueError("parse_gif: not a GIF file (bad signature)")
+    if n < 13:
+        raise ValueError("parse_gif: the logical screen descriptor runs past the end of the file")
+    W, H = int.from_bytes(data[6:8], "little"), int.from_bytes(data[8:10], "little")
+    packed = data[10]
+    background = data[11] if packed & 0x80 else 0                             # PIL reads the background index only beside a global colour table
+    if not (1 <= W <= GIF_MAX_SIDE and 1 <= H <= GIF_MAX_SIDE):
+        raise ValueError(f"parse_gif: a screen is 1 .. {GIF_MAX_SIDE} pixels a side, got {W} x {H}")
+    pos = 13
+
+    def table(flags, what):
+        nonlocal pos
+        entries = 2 << (flags & 7)
+        if pos + 3 * entries > n:
+            raise ValueError(f"parse_gif: {what} runs past the end of the file")
+        t = np.zeros((256, 3), np.uint8)
+        t[:entries] = np.frombuffer(data, np.uint8, 3 * entries, pos).reshape(entries, 3)
+        pos += 3 * entries
+        return t, entries
+
+    def sub_blocks(what):
+        nonlocal pos
+        parts = []
+        while True:
+            if pos >= n:
+                raise ValueError(f"parse_gif: a sub-block of {what} runs past the end of the file (no block terminator)")
+            size = data[pos]
+            if pos + 1 + size > n:
+                raise ValueError(f"parse_gif: a sub-block of {what} runs past the end of the file")
+            parts.append(data[pos + 1:pos + 1 + size])
+            pos += 1 + size
+            if size == 0:
+                return parts[:-1]
+
+    gtable = table(packed, "the global colour table") if packed & 0x80 else None
+    h = GifHeader(W, H, background)
+    control, ended = None, False                                              # the graphic control extension waiting for its image
+    while pos < n:
+        kind = data[pos]
+        pos += 1
+        if kind == 0x3B:
+            ended = True
+            break
+        if kind == 0x21:
+            if pos >= n:
+                raise ValueError("parse_gif: an extension block runs past the end of the file")
+            label = data[pos]
+            pos += 1
+            parts = sub_blocks(f"extension {label:#04x}")
+            if label == 0xF9 and parts and len(parts[0]) >= 4:
+                control = ((parts[0][0] >> 2) & 7, parts[0][3] if parts[0][0] & 1 else None)
+        elif kind == 0x2C:
+            k = len(h.frames)
+            if pos + 9 > n:
+                raise ValueError(f"parse_gif: the image descriptor of frame {k} runs past the end of the file")
+            x, y, w, hh = (int.from_bytes(data[pos + 2 * i:pos + 2 * i + 2], "little") for i in range(4))
+            flags = data[pos + 8]
+            pos += 9
+            ltable = table(flags, f"the local colour table of frame {k}") if flags & 0x80 else gtable
+            if ltable is None:
+                raise ValueError(f"parse_gif: frame {k} has neither a local nor a global colour table (a greyscale GIF is not decoded)")
+            if w == 0 or hh == 0:
+                raise ValueError(f"parse_gif: frame {k} has an empty rectangle ({w} x {hh})")
+            if x + w > W or y + hh > H:
+                raise ValueError(f"parse_gif: the rectangle of frame {k} ({w} x {hh} at ({x}, {y})) leaves the logical screen ({W} x {H}): a canvas "
+                                 "that grows is not decoded")
+            if pos >= n:
+                raise ValueError(f"parse_gif: the image data of frame {k} runs past the end of the file")
+            mcs = data[pos]
+            pos += 1
+            if not 2 <= mcs <= 8:
+                raise ValueError(f"parse_gif: frame {k} has minimum code size {mcs} (2 .. 8)")
+            lzw = b"".join(sub_blocks(f"the image data of frame {k}"))
+            disposal, transparent = control if control is not None else (0, None)
+            h.frames.append(GifFrame(x, y, w, hh, bool(flags & 0x40), mcs, transparent, disposal, ltable[0], ltable[1], lzw))
+            control = None
+        # any other byte: skipped
+    if not h.frames:
+        raise ValueError("parse_gif: no frames" if ended else "parse_gif: missing trailer (the file ends before any image)")
+    return h
+
+
+def gif_operands(h: GifHeader, limit: Optional[int] = None, scratch_bytes: Optional[int] = None):
+    """Host-side operands of one decode: (tab int64 (n, 16), palette uint8 (n, 256, 3), data uint8 (bytes,) padded to a multiple of 16, chunks
+    [(f0, f1, idx_bytes)]).  n = the file's first `limit` frames; the chunks are runs of frames whose palette indices together fit scratch_bytes (one
+    frame at least), and a row's index offset counts from its chunk's start.  The composition rules that need more than the frame itself (the sticky
+    disposal, the colours of the first frame's canvas and of a restore to background) are resolved here."""
+    frames = h.frames if limit is None else h.frames[:max(0, int(limit))]
+    if not frames:
+        raise ValueError("decode_gif_frames: no frames")
+    budget = GIFDEC_SCRATCH_BYTES if scratch_bytes is None else int(scratch_bytes)
+    rgb = lambda c: int(c[0]) | int(c[1]) << 8 | int(c[2]) << 16
+    tab = np.zeros((len(frames), GIF_TAB), np.int64)
+    palette = np.stack([f.palette for f in frames])
+    chunks, begin, sticky, f0, at = [], 0, 0, 0, 0
+    for k, f in enumerate(frames):
+        npix = f.width * f.height
+        if k > f0 and at + npix > budget:
+            chunks.append((f0, k, at))
+            f0, at = k, 0
+        sticky = f.disposal or sticky                                         # bits 0 inherit the last disposal the file named
+        t = tab[k]
+        t[_GD_X], t[_GD_Y], t[_GD_W], t[_GD_H], t[_GD_IDX] = f.x, f.y, f.width, f.height, at
+        t[_GD_BEGIN], t[_GD_END], t[_GD_MCS], t[_GD_LACE] = begin, begin + len(f.lzw), f.min_code_size, int(f.interlace)
+        t[_GD_TRANS] = -1 if f.transparent is None else f.transparent
+        t[_GD_FIRST] = int(k == 0)
+        if k == 0:
+            t[_GD_FILL] = rgb(f.palette[f.transparent if f.transparent is not None else 0])
+        if sticky == 2:
+            index = f.transparent if f.transparent is not None else h.background
+            t[_GD_MODE], t[_GD_COLOUR] = 2, rgb(f.palette[index if k == 0 or index < f.colours else 0])
+        elif sticky >= 3:
+            if k > 0:
+                t[_GD_MODE] = 3
+            elif f.transparent is not None:                                   # the first frame has no earlier canvas: its transparent colour, else nothing
+                t[_GD_MODE], t[_GD_COLOUR] = 2, rgb(f.palette[f.transparent])
+        at += npix
+        begin += len(f.lzw)
+    chunks.append((f0, len(frames), at))
+    blob = b"".join(f.lzw for f in frames)
+    data = np.frombuffer(blob + bytes(16 + (-len(blob)) % 16), np.uint8)
+    return tab, palette, data, chunks
+
+
+def decode_gif_frames(data, device="cuda", out=None, limit=None):
+    """One GIF file (bytes) -> (n, H, W, 3) uint8 RGB on `device`, contiguous, n = its frames (the first `limit` of them; later ones are neither
+    un-LZW'd nor composed): byte for byte what PIL's ImageSequence.Iterator(Image.open(f)) gives after convert("RGB") -- sub-rectangles, local
+    palettes, transparency, interlace and the four disposals composed as PIL composes them.  `out`: a tensor of that shape to write into.  Out-of-scope
+    files raise ValueError before anything is launched; a code stream that does not decode raises RuntimeError naming the first bad frame (the
+    status words are read once per call), and no pixels are returned."""
+    import torch
+    from . import hip
+    h = parse_gif(data)
+    tab, palette, blob, chunks = gif_operands(h, limit)
+    if hip.GIFDEC_TAB != GIF_TAB:
+        raise RuntimeError(f"decode_gif_frames: the binding's table row has {hip.GIFDEC_TAB} words, this module builds {GIF_TAB}")
+    n, H, W = len(tab), h.height, h.width
+    dev = torch.device(device)
+    if out is None:
+        out = torch.empty((n, H, W, 3), device=dev, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError(f"decode_gif_frames: out must be contiguous uint8 ({n}, {H}, {W}, 3) on the device")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_data, d_tab, d_pal = up(blob.copy()), up(tab), up(palette)
+    status = torch.empty((n,), device=dev, dtype=torch.int32)
+    idx = torch.empty((max(c[2] for c in chunks),), device=dev, dtype=torch.uint8)
+    carry = torch.empty((2, H, W, 3), device=dev, dtype=torch.uint8)          # canvas and pending restore, from one chunk to the next
+    for f0, f1, idx_bytes in chunks:
+        hip.gif_unlzw(d_data, d_tab[f0:f1], idx_bytes, out=(idx[:idx_bytes], status[f0:f1]))
+        hip.gif_compose(d_tab[f0:f1], idx[:idx_bytes], d_pal[f0:f1], carry, H, W, out=out[f0:f1])
+    st = status.cpu().numpy()                                                  # the one read of the status words (it also orders the launches)
+    bad = np.flatnonzero(st)
+    if bad.size:
+        f = int(bad[0])
+        raise RuntimeError(f"decode_gif_frames: frame {f}, image data: {GIF_STATUS_TEXT.get(int(st[f]), f'status {int(st[f])}')}")
+    return out
+
+
 def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
     """(L, H, W, 3) uint8 RGB frames of `path` on `device`, decoded there: a Motion-JPEG .avi (what video_out.write_avi writes, or any stock
-    tool's `-c:v mjpeg`), a directory whose images are all .jpg / .jpeg or all .png (sorted by name; a .png file gives its first frame), or one
-    .png / .apng file, animated or not (what video_out.write_apng / write_png write).  Everything else raises: inputs.read_frames is the host route,
-    and the caller chooses it."""
+    tool's `-c:v mjpeg`), a directory whose images are all .jpg / .jpeg or all .png (sorted by name; a .png file gives its first frame), one
+    .png / .apng file, animated or not (what video_out.write_apng / write_png write), or one .gif file (what video_out.write_gif or PIL writes).
+    Everything else raises: inputs.read_frames is the host route, and the caller chooses it."""
     from .inputs import IMAGE_SUFFIXES, mjpeg_avi_frames
     p = Path(path)
     if not p.exists():
@@ -567,11 +776,15 @@ def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
         if not h.streams:
             raise RuntimeError(f"read_frames_device: no frames in {p}")
         return _decode_png_operands(png_batch_operands(None, [h]), device)
+    elif p.suffix.lower() == ".gif":
+        if limit is not None and limit < 1:
+            raise RuntimeError(f"read_frames_device: no frames in {p}")
+        return decode_gif_frames(p.read_bytes(), device, limit=limit)
     else:
         jpegs = mjpeg_avi_frames(p, limit) if p.suffix.lower() == ".avi" else None
         if jpegs is None:
-            raise RuntimeError(f"read_frames_device: {p.name} is neither a Motion-JPEG .avi, a .png / .apng file nor a directory of .jpg or .png "
-                               "frames; use inputs.read_frames for other inputs")
+            raise RuntimeError(f"read_frames_device: {p.name} is neither a Motion-JPEG .avi, a .png / .apng file, a .gif file nor a directory of "
+                               ".jpg or .png frames; use inputs.read_frames for other inputs")
     if not jpegs:
         raise RuntimeError(f"read_frames_device: no frames in {p}")
     return decode_jpeg_frames(jpegs, device)

@@ -12,7 +12,8 @@ pose / mask / audio inputs, everything a pure function of names (mmgt_amd/synthe
 Without --synthetic the inputs are FILES, as in the reference (scripts/pose2vid.py:196-271): the reference image through PIL, the
 pose / mask clips as directories of images, .npy stacks or animated images (mmgt_amd/inputs.py: video containers need PyAV / cv2,
 which this build does not include, and say so), the masks blurred / resampled on the device (mmgt_amd/conditioning.py).  --decoder device
-reads Motion-JPEG .avi clips or directories of .jpg frames on the GPU instead (mmgt_amd/video_in.py) and runs the
+reads Motion-JPEG .avi clips, directories of .jpg or .png frames, .png / .apng files or .gif files on the GPU instead (mmgt_amd/video_in.py,
+DESIGN 4e, 4h, 4i) and runs the
 resizes of the pose frames and of the reference image there too (PIL's resampling, byte for byte: DESIGN 4f).  Weights
 come from the checkpoints the config yaml names (:137-190) -- or, with --random-weights, from the hash-seeded initialisation (no
 checkpoint exists in this image).  The clip is written as .gif / .npy / Motion-JPEG .avi / lossless .apng or a directory of .png files (mp4 muxing is out of scope:
@@ -62,7 +63,7 @@ def parse_args():
                         "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
     p.add_argument("--decoder", default="pil", choices=["pil", "device"],
                    help="how --pose_path and the mask paths are read: pil = on the host (any input read_frames takes); device = Motion-JPEG "
-                        ".avi, a directory of .jpg or of .png frames, or a .png / .apng file, decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
+                        ".avi, a directory of .jpg or of .png frames, a .png / .apng file or a .gif file, decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
                         "resized on the device too (a baseline .jpg or a .png is also decoded there)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
@@ -148,8 +149,8 @@ def build_from_checkpoints(cfg_path, num_c, dev, dtype):
 
 
 def load_inputs(a, dev):
-    """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG
-    and PNG / APNG on the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
+    """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG,
+    PNG / APNG and GIF on the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
     from mmgt_amd import inputs
     device = getattr(a, "decoder", "pil") == "device"
     if device:
