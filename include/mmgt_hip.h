@@ -482,6 +482,28 @@ int mmgt_png_deflate(const unsigned char* data, const unsigned int* codes, const
  * Nothing outside slots_words / out_bytes is read or written. */
 int mmgt_png_pack(const unsigned int* slots, const long long* slot_off, long long slots_words, const long long* bit_off, unsigned char* out,
                   const long long* out_off, long long out_bytes, int n, int strips, void* stream);
+/* ---- WebP lossless output path (csrc/webp.hip, csrc/webp_core.h, mmgt_amd/video_out.py): one VP8L bitstream per RGB frame.  Every buffer
+ * is a device pointer.  Like every entry: 0 on success, else mmgt_last_error() has the text and nothing was launched.
+ * predict: frames (n, H, W, 3) u8 RGB -> modes (n, bh, bw) u8 with bh = ceil(H / 16), bw = ceil(W / 16): per block of 16 x 16 pixels the predictor
+ * mode 0 .. 13 with the smallest sum of min(v, 256 - v) over its residuals' r, g, b, the lowest mode on a tie; res (n, H, W) = the residuals as ARGB
+ * words, taken per channel mod 256 from the subtract-green pixels (255, r - g, g, b - g).  n, H, W >= 1, H, W <= 16384. */
+int mmgt_webp_predict(const unsigned char* frames, unsigned char* modes, unsigned int* res, int n, int H, int W, void* stream);
+/* The two passes of the coder over ANY words: res (n, frame_px), every row cut into strips = ceil(frame_px / strip_px) strips of strip_px (the last
+ * may be shorter), 1 <= frame_px <= 2^28.  A strip's tokens: position 0 is a literal; at p >= 1 with r = words from p on that equal word p - 1 (at most
+ * 4096), r >= 3 is a match of length r from the left pixel, else word p is a literal.
+ * histogram: hist (n * strips, MMGT_WEBP_HIST_WORDS) = how often each symbol occurs: [0, 256) a literal's green, [256, 280) a match's length prefix,
+ * [280, 536) a literal's red, [536, 792) its blue, [792] the matches (every entry is written).
+ * code: strip s of frame f codes its tokens with codes + f * 792 (green / length, red, blue as in hist; entry = the symbol's code, bit-reversed for an
+ * LSB-first stream, | its length << 16, length 0 for the symbol of a one-symbol code; a literal is green, red, blue, a match its prefix code and extra
+ * bits; alpha and the distance take no bits), LSB-first into the words slot_off[k] .. slot_off[k + 1] - 1 of slots with k = f * (strips + 1) + 1 + s,
+ * and bits[f * strips + s] = the bits it took.  Slot f * (strips + 1) is frame f's header: header[header_off[f] .. header_off[f + 1]) is copied there
+ * (header_off has n + 1 entries, slot_off n * (strips + 1) + 1).  No word outside a slot, slots_words or header_words is touched; every word below
+ * ceil(bits / 32) of a slot is written.  mmgt_png_pack joins a frame's strips + 1 slots. */
+#define MMGT_WEBP_HIST_WORDS 793
+int mmgt_webp_histogram(const unsigned int* res, unsigned int* hist, int n, long long frame_px, long long strip_px, void* stream);
+int mmgt_webp_code(const unsigned int* res, const unsigned int* codes, const unsigned int* header, const long long* header_off, long long header_words,
+                   unsigned int* slots, const long long* slot_off, long long slots_words, long long* bits, int n, long long frame_px,
+                   long long strip_px, void* stream);
 /* ---- PNG input path (csrc/pngdec.hip, csrc/pngdec_core.h, mmgt_amd/video_in.py): non-interlaced PNG / APNG frames of one geometry.  Every
  * buffer is a device pointer; the status words are those of csrc/pngdec_core.h (0: fine).  Arguments outside the stated range: non-zero, nothing
  * launched, mmgt_last_error() says "range".

@@ -129,6 +129,10 @@ _SIGS = {
     "mmgt_png_deflate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong,
                                  ctypes.c_longlong, c_void_p]),
     "mmgt_png_pack": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
+    "mmgt_webp_predict": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_webp_histogram": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
+    "mmgt_webp_code": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int,
+                               ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
     "mmgt_png_inflate": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "mmgt_png_unfilter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_png_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
@@ -1334,6 +1338,111 @@ def png_pack(slots, want_bits, out=None):
         f1 = min(n, f0 + 65535)
         d_off, d_bit, d_out = up(off[f0 * strips:f1 * strips + 1]), up(bit_off[f0:f1]), up(out_off[f0:f1 + 1])                      # alive until launched
         _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, strips,
+                                   _stream()), "mmgt_png_pack")
+    return out, out_off
+
+
+# ------------------------------------------------------------------------------------------------------------ WebP lossless (csrc/webp.hip)
+
+WEBP_PREDICTOR_BITS = 4             # WP_PREDICTOR_BITS: blocks of 16 x 16 pixels choose a predictor mode
+WEBP_HIST_WORDS = 793               # MMGT_WEBP_HIST_WORDS: green + length [280], red [256], blue [256], matches
+WEBP_CODE_WORDS = 792               # a frame's code tables: green + length, red, blue
+
+
+def webp_predict(frames, out=None):
+    """(n, H, W, 3) uint8 RGB -> (modes (n, bh, bw) uint8, res (n, H, W) int32): every 16 x 16 block's predictor mode and the residuals as ARGB
+    words (see mmgt_webp_predict).  `out` = (modes, res) to write into."""
+    n, H, W = _gif_frames(frames, "webp_predict")
+    B = 1 << WEBP_PREDICTOR_BITS
+    bh, bw = -(-H // B), -(-W // B)
+    if out is None:
+        out = (torch.empty((n, bh, bw), device=frames.device, dtype=torch.uint8), torch.empty((n, H, W), device=frames.device, dtype=torch.int32))
+    modes, res = out
+    assert modes.shape == (n, bh, bw) and modes.dtype == torch.uint8 and modes.is_contiguous()
+    assert res.shape == (n, H, W) and res.dtype == torch.int32 and res.is_contiguous()
+    _check(lib().mmgt_webp_predict(_ptr(frames), _ptr(modes), _ptr(res), n, H, W, _stream()), "mmgt_webp_predict")
+    return modes, res
+
+
+def _webp_data(data, strip_px, what):
+    _dev(data)
+    if data.dtype != torch.int32 or data.dim() != 2 or not data.is_contiguous() or data.shape[0] < 1 or data.shape[1] < 1 or int(strip_px) < 1:
+        raise RuntimeError(f"{what}: data must be contiguous int32 (n, frame_px), strip_px at least 1")
+    n, frame_px = data.shape
+    return n, frame_px, -(-frame_px // int(strip_px))
+
+
+def webp_histogram(data, strip_px, out=None):
+    """data (n, frame_px) int32, any words -> (n, strips, 793): how often each green / length, red and blue symbol occurs in the tokens of every
+    strip of strip_px pixels, and its matches (see mmgt_webp_histogram).  The counts are uint32 held in an int32 tensor."""
+    n, frame_px, strips = _webp_data(data, strip_px, "webp_histogram")
+    if out is None:
+        out = torch.empty((n, strips, WEBP_HIST_WORDS), device=data.device, dtype=torch.int32)
+    assert out.shape == (n, strips, WEBP_HIST_WORDS) and out.dtype == torch.int32 and out.is_contiguous()
+    _check(lib().mmgt_webp_histogram(_ptr(data), _ptr(out), n, frame_px, int(strip_px), _stream()), "mmgt_webp_histogram")
+    return out
+
+
+def webp_slot_offsets(want_bits):
+    """Exact bit counts (n, 1 + strips), a frame's header first -> word offsets (n * (1 + strips) + 1,) int64 of slots that hold them, each a whole
+    number of 32-bit words.  A strip may hold no bit at all (every symbol the only one of its alphabet); a header never does."""
+    import numpy as np
+    w = np.asarray(want_bits, np.int64)
+    if w.ndim != 2 or w.shape[1] < 2 or w.shape[0] < 1 or (w < 0).any() or (w[:, 0] < 1).any():
+        raise RuntimeError("webp: bit counts are (n, 1 + strips), none negative, every header at least one bit")
+    return np.concatenate([[0], np.cumsum((w.reshape(-1) + 31) // 32)]).astype(np.int64)
+
+
+def webp_code(data, strip_px, codes, headers, want_bits, out=None):
+    """Codes every strip of data (n, frame_px) into its slot and copies the frames' headers into theirs: host arrays codes (n, 792) uint32, headers =
+    n byte strings (a frame's header bits, LSB-first) and want_bits (n, 1 + strips) int64, the bit count of each header and strip that sizes and
+    places its slot (webp_slot_offsets) -> (slots (words,) int32, bits (n, strips) int64 as the device counted them).  `out` = (slots, bits)."""
+    import numpy as np
+    n, frame_px, strips = _webp_data(data, strip_px, "webp_code")
+    codes, want = np.ascontiguousarray(codes, np.uint32), np.asarray(want_bits, np.int64)
+    if codes.shape != (n, WEBP_CODE_WORDS) or want.shape != (n, strips + 1) or len(headers) != n:
+        raise RuntimeError(f"webp_code: tables do not match {n} x {strips} strips")
+    off = webp_slot_offsets(want)
+    hwords = (want[:, 0] + 31) // 32
+    if any(len(h) > 4 * int(k) for h, k in zip(headers, hwords)):
+        raise RuntimeError("webp_code: a header is longer than its bit count")
+    hoff = np.concatenate([[0], np.cumsum(hwords)]).astype(np.int64)
+    hbuf = np.zeros(4 * int(hoff[-1]), np.uint8)
+    for f, h in enumerate(headers):
+        hbuf[4 * hoff[f]:4 * hoff[f] + len(h)] = np.frombuffer(h, np.uint8)
+    up = lambda a, dt: torch.from_numpy(a.view(dt)).to(data.device)
+    if out is None:
+        out = (torch.empty((max(1, int(off[-1])),), device=data.device, dtype=torch.int32),
+               torch.empty((n, strips), device=data.device, dtype=torch.int64))
+    slots, bits = out
+    assert slots.dim() == 1 and slots.numel() >= int(off[-1]) and slots.dtype == torch.int32 and slots.is_contiguous()
+    assert bits.shape == (n, strips) and bits.dtype == torch.int64 and bits.is_contiguous()
+    codes, hbuf, d_hoff, d_off = up(codes, np.int32), up(hbuf, np.int32), up(hoff, np.int64), up(off, np.int64)      # alive until launched
+    _check(lib().mmgt_webp_code(_ptr(data), _ptr(codes), _ptr(hbuf), _ptr(d_hoff), hbuf.numel(), _ptr(slots), _ptr(d_off), slots.numel(), _ptr(bits),
+                                n, frame_px, int(strip_px), _stream()), "mmgt_webp_code")
+    return slots, bits
+
+
+def webp_pack(slots, want_bits, out=None):
+    """The slots of webp_code, laid out by the same want_bits (n, 1 + strips) -> (packed (bytes,) uint8, out_off (n + 1,) host int64): frame f's VP8L
+    payload, its header and strips joined bit by bit and padded with zero bits to a byte, is packed[out_off[f]:out_off[f + 1]].  The join is
+    mmgt_png_pack's, with the header as one more slot.  `out` = packed to write into."""
+    import numpy as np
+    _dev(slots)
+    w = np.asarray(want_bits, np.int64)
+    off = webp_slot_offsets(w)
+    n, k = w.shape
+    bit_off = np.concatenate([np.zeros((n, 1), np.int64), np.cumsum(w, axis=1)], axis=1)
+    out_off = np.concatenate([[0], np.cumsum((bit_off[:, -1] + 7) // 8)]).astype(np.int64)
+    if out is None:
+        out = torch.empty((int(out_off[-1]),), device=slots.device, dtype=torch.uint8)
+    assert slots.dim() == 1 and slots.numel() >= int(off[-1]) and slots.dtype == torch.int32 and slots.is_contiguous()
+    assert out.dim() == 1 and out.numel() >= int(out_off[-1]) and out.dtype == torch.uint8 and out.is_contiguous()
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(slots.device)
+    for f0 in range(0, n, 65535):                                  # the launch's grid holds a frame per y index
+        f1 = min(n, f0 + 65535)
+        d_off, d_bit, d_out = up(off[f0 * k:f1 * k + 1]), up(bit_off[f0:f1]), up(out_off[f0:f1 + 1])                                # alive until launched
+        _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, k,
                                    _stream()), "mmgt_png_pack")
     return out, out_off
 

@@ -6,7 +6,9 @@ encodes with PyAV / libx264, which is not part of this build: .gif goes through 
 (csrc/mjpeg.hip; encode_jpeg_frames) in a RIFF AVI 1.0 container with an optional PCM sound track (write_avi).  gif_encoder="device" is a second,
 opt-in .gif writer: one palette for the clip (gif_palette, gif_lut), index map, LZW and sub-block packing on the device (csrc/gif.hip;
 encode_gif_frames) and the GIF89a container here (write_gif).  .apng / .png are the lossless output: scanline filters and deflate on the device
-(csrc/png.hip; encode_png_frames), Huffman code lengths, block headers and the PNG / APNG chunks here (write_png, write_png_sequence, write_apng)."""
+(csrc/png.hip; encode_png_frames), Huffman code lengths, block headers and the PNG / APNG chunks here (write_png, write_png_sequence, write_apng).
+.webp is the second lossless output, WebP lossless / animated WebP: subtract green, predictor choice and prefix coding on the device (csrc/webp.hip;
+encode_webp_frames), the five codes of a frame, its header and the RIFF chunks here (webp_prefix_code, webp_frame_header, write_webp)."""
 import os
 import struct
 from pathlib import Path
@@ -630,6 +632,242 @@ def write_apng(path, blobs, W, H, fps, loop=0):
     return _write(path, b"".join(out))
 
 
+# ---- WebP lossless / animated WebP: VP8L frames, predicted and coded on the device ----------------------------------------------------
+WEBP_STRIP_ROWS = 64                # rows per strip of encode_webp_frames: the strip_rows sweep of tools/bench_webp.py
+WEBP_SCRATCH_BYTES = 256 << 20      # encode_webp_frames holds at most this much residuals, strip slots, packed frames and tables per set of launches
+WEBP_MAX_SIDE = 16384               # VP8L's 14-bit sizes
+WEBP_PREDICTOR_BITS = 4             # blocks of 16 x 16 pixels choose a predictor mode (csrc/webp_core.h: WP_PREDICTOR_BITS)
+WEBP_MAX_BYTES = (1 << 32) - 1      # a RIFF size is 32 bits
+_WEBP_CL_ORDER = np.array([17, 18, 0, 1, 2, 3, 4, 5, 16, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15])
+# bits that follow each symbol of the green + length alphabet: a length prefix 2 hb + sb from 4 on takes hb - 1 extra bits
+_WEBP_GREEN_EXTRA = np.zeros(280, np.int64)
+_WEBP_GREEN_EXTRA[260:] = np.arange(4, 24) // 2 - 1
+
+
+def _webp_rle_code_lengths(seq):
+    """The code lengths as (symbol, extra bits, extra value) of VP8L's code-length alphabet.  Zeros: 18 for min(run, 138) while 11 or more are left,
+    then 17 for 3 .. 10, then single zeros.  `prev` starts at 8 and only a length written as itself changes it: a non-zero length equal to prev with
+    3 or more equal lengths from here on is 16 for min(run, 6) of them; otherwise the length itself."""
+    seq = np.asarray(seq)
+    cut = np.flatnonzero(np.diff(seq)) + 1
+    starts = np.concatenate([[0], cut])
+    runs = np.diff(np.concatenate([starts, [seq.size]]))
+    out, prev = [], 8
+    for v, run in zip(seq[starts].tolist(), runs.tolist()):
+        if v == 0:
+            while run >= 11:
+                k = min(run, 138)
+                out.append((18, 7, k - 11))
+                run -= k
+            if run >= 3:
+                out.append((17, 3, run - 3))
+                run = 0
+            out += [(0, 0, 0)] * run
+            continue
+        while run:
+            if v == prev and run >= 3:
+                k = min(run, 6)
+                out.append((16, 2, k - 3))
+                run -= k
+            else:
+                out.append((v, 0, 0))
+                prev = v
+                run -= 1
+    return out
+
+
+def webp_prefix_code(counts):
+    """Counts per symbol of one alphabet -> (lengths as the pixels are coded with them, the code's description as an LSB-first bit string, its bit
+    count).  One used symbol (below 256), or none (then symbol 0): a simple code, bits 1 0 and 0 + 1 bit or 1 + 8 bits of symbol, and the symbol
+    costs NO bits, so the lengths are all zero.  Otherwise a normal code: bit 0, the count of code-length-code lengths - 4 (trailing zeros in
+    VP8L's order trimmed, at least 4), those lengths at 3 bits each, bit 0 (max_symbol is not used), then the alphabet's lengths
+    (deflate_code_lengths, limit 15) run-length coded (_webp_rle_code_lengths) with the code-length code (limit 7).  A code-length code with ONE used
+    symbol is read with zero bits per token, whatever length it states: then only the extra bits are written."""
+    h = np.asarray(counts).astype(np.int64).reshape(-1)
+    used = np.flatnonzero(h)
+    if used.size <= 1:
+        s = int(used[0]) if used.size else 0
+        if s >= 256:
+            raise ValueError(f"webp_prefix_code: the only used symbol is {s}; a simple code names symbols below 256")
+        acc, nb = (0b01 | 0 << 2 | s << 3, 4) if s < 2 else (0b01 | 1 << 2 | s << 3, 11)
+        return np.zeros(h.size, np.int64), acc, nb
+    lengths = deflate_code_lengths(h, 15)
+    syms = _webp_rle_code_lengths(lengths)
+    cl = deflate_code_lengths(np.bincount([s for s, _, _ in syms], minlength=19), 7)
+    codes = _canonical_codes(cl)
+    ncl = max(4, int(np.flatnonzero(cl[_WEBP_CL_ORDER])[-1]) + 1)
+    one = int(np.count_nonzero(cl)) == 1
+    acc, nb = (ncl - 4) << 1, 5
+    for k in range(ncl):
+        acc |= int(cl[_WEBP_CL_ORDER[k]]) << nb
+        nb += 3
+    nb += 1
+    cl, codes = ([0] * 19, [0] * 19) if one else (cl.tolist(), codes.tolist())
+    for s, eb, ev in syms:
+        acc |= (codes[s] | ev << cl[s]) << nb
+        nb += cl[s] + eb
+    return lengths, acc, nb
+
+
+def _webp_code_bits(symbols, lengths):
+    """Symbols coded one after the other with the canonical code of `lengths` -> (LSB-first bit string, bit count)."""
+    lengths = np.asarray(lengths, np.int64)
+    ln = lengths[symbols]
+    codes = _canonical_codes(lengths)[symbols]
+    bits = (codes[:, None] >> np.arange(15)) & 1
+    flat = bits[np.arange(15) < ln[:, None]].astype(np.uint8)
+    return int.from_bytes(np.packbits(flat, bitorder="little").tobytes(), "little"), int(ln.sum())
+
+
+def webp_frame_tables(hist):
+    """A frame's histogram u32[793] (the sum of its strips': green + length [280], red [256], blue [256], matches) -> (code tables u32[792] =
+    bit-reversed code | length << 16 as csrc/webp.hip reads them, bits that one occurrence of each of the 793 entries takes, the five codes'
+    description as (bit string, bit count)).  Alpha is 0 in every literal and the distance is prefix symbol 1 (the left pixel) in every match."""
+    h = np.asarray(hist).astype(np.int64).reshape(-1)
+    if h.size != 793:
+        raise ValueError(f"webp_frame_tables: expected 793 counts, got {h.size}")
+    alpha, dist = np.zeros(256, np.int64), np.zeros(40, np.int64)
+    alpha[0], dist[1] = h[:256].sum(), h[792]
+    acc, nb, lens = 0, 0, []
+    for counts in (h[:280], h[280:536], h[536:792], alpha, dist):
+        ln, a, k = webp_prefix_code(counts)
+        acc |= a << nb
+        nb += k
+        lens.append(ln)
+    table = np.concatenate([_canonical_codes(ln) | ln << 16 for ln in lens[:3]]).astype(np.uint32)
+    cost = np.concatenate([lens[0] + _WEBP_GREEN_EXTRA, lens[1], lens[2], [0]])
+    return table, cost, (acc, nb)
+
+
+def webp_frame_header(W, H, modes, codes):
+    """Everything of a VP8L bitstream that stands before the pixels, as (bytes, bit count), the bits past the count zero: signature 0x2f, W - 1 and
+    H - 1 in 14 bits each, alpha-is-used 0, version 0; the subtract-green transform (1, type 2); the predictor transform (1, type 0, block bits - 2
+    in 3 bits) with its sub-image of `modes` (bh, bw): no colour cache, five codes, the pixels (255, 0, mode, 0) as literals, of which only the
+    mode takes bits; then 0 0 0 (no further transform, no colour cache, no meta prefix codes) and `codes`, the five codes of the frame as
+    webp_frame_tables describes them."""
+    W, H = int(W), int(H)
+    if not (1 <= W <= WEBP_MAX_SIDE and 1 <= H <= WEBP_MAX_SIDE):
+        raise ValueError(f"webp_frame_header: a frame is 1 .. {WEBP_MAX_SIDE} pixels a side, got {W} x {H}")
+    m = np.asarray(modes).astype(np.int64)
+    B = 1 << WEBP_PREDICTOR_BITS
+    if m.shape != (-(-H // B), -(-W // B)) or m.min() < 0 or m.max() > 13:
+        raise ValueError(f"webp_frame_header: modes must be ({-(-H // B)}, {-(-W // B)}) values 0 .. 13")
+    m = m.reshape(-1)
+    acc = 0x2F | (W - 1) << 8 | (H - 1) << 22                                   # alpha-is-used and the version: four zero bits
+    nb = 40
+    acc |= (1 | 2 << 1) << nb                                                    # subtract green
+    nb += 3
+    acc |= (1 | 0 << 1 | (WEBP_PREDICTOR_BITS - 2) << 3) << nb                   # predictor; then its sub-image's colour-cache bit 0
+    nb += 7
+    zero, a255 = np.zeros(256, np.int64), np.zeros(256, np.int64)
+    zero[0] = a255[255] = m.size
+    ml = None
+    for counts in (np.bincount(m, minlength=280), zero, zero, a255, np.zeros(40, np.int64)):
+        ln, a, k = webp_prefix_code(counts)
+        ml = ln if ml is None else ml
+        acc |= a << nb
+        nb += k
+    a, k = _webp_code_bits(m, ml)
+    acc |= a << nb
+    nb += k + 3                                                                  # 0 0 0
+    acc |= codes[0] << nb
+    nb += codes[1]
+    return acc.to_bytes((nb + 7) // 8, "little"), nb
+
+
+def encode_webp_frames(frames_u8, strip_rows=None) -> list:
+    """(n, H, W, 3) uint8 RGB frames (a CUDA tensor, or host data that is uploaded) -> n byte strings, each one frame's VP8L bitstream (write_webp
+    puts the chunks around it).  Subtract green, predictor choice, tokens, prefix coding and bit packing run on the device (csrc/webp.hip); the host
+    builds each frame's five codes and its header from the device's block modes and symbol histograms, knows every strip's bit count from them,
+    and receives ONE buffer of finished bytes per set of launches.  The bytes are the same on every call; DESIGN.md 4j defines them."""
+    from . import hip
+    x = torch.as_tensor(frames_u8)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"encode_webp_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
+    n, H, W, _ = x.shape
+    if n == 0 or H == 0 or W == 0:
+        raise ValueError(f"encode_webp_frames: empty clip {tuple(x.shape)}")
+    if H > WEBP_MAX_SIDE or W > WEBP_MAX_SIDE:
+        raise ValueError(f"encode_webp_frames: a frame is at most {WEBP_MAX_SIDE} x {WEBP_MAX_SIDE}, got {W} x {H}")
+    strip_rows = int(WEBP_STRIP_ROWS if strip_rows is None else strip_rows)
+    if strip_rows < 1:
+        raise ValueError(f"encode_webp_frames: strip_rows must be at least 1, got {strip_rows}")
+    strip_rows = min(strip_rows, H)
+    if not x.is_cuda:
+        x = x.cuda()
+    x = x.contiguous()
+    strips = -(-H // strip_rows)
+    blocks = -(-H >> WEBP_PREDICTOR_BITS) * -(-W >> WEBP_PREDICTOR_BITS)
+    # residual words; slots and output, each at most 45 bits a pixel; the header with its modes; histograms and offsets
+    per_frame = 4 * H * W + 2 * 6 * H * W + 3 * (blocks + 2048) + strips * (793 * 4 + 64) + 792 * 4
+    per_call = max(1, WEBP_SCRATCH_BYTES // per_frame)
+    blobs = []
+    for f0 in range(0, n, per_call):
+        modes, res = hip.webp_predict(x[f0:f0 + per_call])
+        k = res.shape[0]
+        data = res.view(k, H * W)
+        hist = hip.webp_histogram(data, strip_rows * W).cpu().numpy().view(np.uint32).astype(np.int64)          # (k, strips, 793)
+        modes = modes.cpu().numpy()
+        codes, heads, want = np.empty((k, 792), np.uint32), [], np.empty((k, 1 + strips), np.int64)
+        for f in range(k):
+            codes[f], cost, described = webp_frame_tables(hist[f].sum(0))
+            head, want[f, 0] = webp_frame_header(W, H, modes[f], described)
+            heads.append(head)
+            want[f, 1:] = hist[f] @ cost
+        slots, bits = hip.webp_code(data, strip_rows * W, codes, heads, want)
+        packed, out_off = hip.webp_pack(slots, want)
+        bits = bits.cpu().numpy()
+        if not np.array_equal(bits, want[:, 1:]):
+            bad = tuple(np.argwhere(bits != want[:, 1:])[0])
+            raise RuntimeError(f"encode_webp_frames: strip {bad} took {bits[bad]} bits on the device, its histogram gives {want[:, 1:][bad]} "
+                               "(mmgt_webp_code)")
+        packed = packed.cpu().numpy()
+        blobs += [packed[out_off[f]:out_off[f + 1]].tobytes() for f in range(k)]
+    return blobs
+
+
+def _u24(v):
+    return struct.pack("<I", v)[:3]
+
+
+def webp_duration_ms(fps) -> int:
+    """A frame's duration in whole milliseconds, at least 1: 25 fps -> 40, 8 -> 125, 29.97 -> 33."""
+    return max(1, int(1000 / float(fps) + 0.5))
+
+
+def write_webp(path, blobs, W, H, fps, loop=0):
+    """VP8L payloads of encode_webp_frames -> a WebP file.  One frame: RIFF 'WEBP' { VP8L }.  Several: RIFF 'WEBP' { VP8X (flags 0x02 = animation,
+    canvas W - 1 and H - 1 in 24 bits), ANIM (background 0, `loop` plays, 0 = for ever), per frame ANMF (offset 0 0, W - 1, H - 1, the duration in ms
+    in 24 bits, flags 0x02 = do not blend, do not dispose) wrapping one VP8L chunk }.  Chunks are padded to even length.  Returns the bytes
+    written."""
+    blobs = [bytes(b) for b in blobs]
+    W, H = int(W), int(H)
+    if not blobs:
+        raise ValueError("write_webp: no frames")
+    if not (1 <= W <= WEBP_MAX_SIDE and 1 <= H <= WEBP_MAX_SIDE):
+        raise ValueError(f"write_webp: a frame is 1 .. {WEBP_MAX_SIDE} pixels a side, got {W} x {H}")
+    if not float(fps) > 0:
+        raise ValueError(f"write_webp: fps must be positive, got {fps}")
+    loop = int(loop)
+    if not 0 <= loop <= 65535:
+        raise ValueError(f"write_webp: loop must be 0 .. 65535, got {loop}")
+    duration = webp_duration_ms(fps)
+    if duration > (1 << 24) - 1:
+        raise ValueError(f"write_webp: a frame's duration is at most 2^24 - 1 ms, got fps = {fps}")
+    total = 12 + sum(8 + len(b) + (len(b) & 1) for b in blobs) + (0 if len(blobs) == 1 else 18 + 14 + 24 * len(blobs))
+    if total > WEBP_MAX_BYTES:
+        raise ValueError(f"write_webp: {path} would pass 4 GiB - 1 ({total} bytes); a RIFF size is 32 bits")
+    if len(blobs) == 1:
+        body = b"WEBP" + _chunk(b"VP8L", blobs[0])
+    else:
+        size = _u24(W - 1) + _u24(H - 1)
+        out = [b"WEBP", _chunk(b"VP8X", b"\x02\0\0\0" + size), _chunk(b"ANIM", struct.pack("<IH", 0, loop))]
+        out += [_chunk(b"ANMF", _u24(0) + _u24(0) + size + _u24(duration) + b"\x02" + _chunk(b"VP8L", b)) for b in blobs]
+        body = b"".join(out)
+    assert len(body) + 8 == total
+    return _write(path, b"RIFF" + struct.pack("<I", len(body)) + body)
+
+
 def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90, gif_encoder="pil"):
     if gif_encoder not in ("pil", "device"):
         raise ValueError(f"gif_encoder must be 'pil' or 'device', got {gif_encoder!r}")
@@ -656,6 +894,8 @@ def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=
         write_avi(path, encode_jpeg_frames(frames, quality), frames.shape[2], frames.shape[1], fps)
     elif fmt in (".apng", ".png"):                                          # lossless; one frame gives an ordinary PNG
         write_apng(path, encode_png_frames(frames), frames.shape[2], frames.shape[1], fps)
+    elif fmt == ".webp":                                                    # lossless; one frame gives a plain VP8L file
+        write_webp(path, encode_webp_frames(frames), frames.shape[2], frames.shape[1], fps)
     elif fmt == ".mp4":
         raise RuntimeError("mp4 output needs PyAV / libx264 (src/utils/util.py:83-97), which this build does not include: "
                            "write .gif or .npy, or hand frames_uint8() to your encoder")

@@ -14,7 +14,7 @@ The chain is the reference's (line numbers of its scripts/audio2vid.py):
      reference drawers and of the OpenCV primitives under them; cv2 itself is not in this image, so that restatement is parity-unpinned), no files
   4. wav2vec2 features of the waveform (:420-426, src/dataset/audio_processor.py:76-131) -> mmgt_amd.wav2vec.Wav2VecModel (HIP);
      mask blur + 4-level pyramid (:453-476), audio window stack + AudioProjModel (:426,439-441) -> device kernels
-  5. Pose2VideoPipeline (:484-498), frames converted to uint8 on the device, written as .npy / .gif.
+  5. Pose2VideoPipeline (:484-498), frames converted to uint8 on the device, written as .npy / .gif / .avi / .apng / .png files / .webp.
 
 --synthetic: random-init weights of the reference architectures (no checkpoints ship with the reference), a synthetic 16-kHz
 waveform for the wav2vec2 leg, and synthetic WavLM + baseline features for SMGA (librosa extraction and vocal separation are host-side
@@ -57,9 +57,10 @@ def parse_args():
     p.add_argument("--motion_diffusion_ckpt", type=str, default="./pretrained_weights/MMGT_pretrained/stage_1/audio2pose_best_model.pt")
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--format", default="npy", choices=["npy", "gif", "avi", "apng", "pngs"],
+    p.add_argument("--format", default="npy", choices=["npy", "gif", "avi", "apng", "pngs", "webp"],
                    help="avi = Motion-JPEG encoded on the device, with the samples of --audio_path as its PCM sound track; apng = lossless animated "
-                        "PNG, pngs = a directory of 0000.png, 0001.png, ..., both filtered and deflated on the device (mmgt_amd.video_out)")
+                        "PNG, pngs = a directory of 0000.png, 0001.png, ..., both filtered and deflated on the device; webp = lossless animated "
+                        "WebP, predicted and prefix-coded on the device (mmgt_amd.video_out)")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "

@@ -16,7 +16,7 @@ reads Motion-JPEG .avi clips, directories of .jpg or .png frames, .png / .apng f
 DESIGN 4e, 4h, 4i) and runs the
 resizes of the pose frames and of the reference image there too (PIL's resampling, byte for byte: DESIGN 4f).  Weights
 come from the checkpoints the config yaml names (:137-190) -- or, with --random-weights, from the hash-seeded initialisation (no
-checkpoint exists in this image).  The clip is written as .gif / .npy / Motion-JPEG .avi / lossless .apng or a directory of .png files (mp4 muxing is out of scope:
+checkpoint exists in this image).  The clip is written as .gif / .npy / Motion-JPEG .avi / lossless .apng, a directory of .png files or lossless animated .webp (mp4 muxing is out of scope:
 mmgt_amd/video_out.py).
 """
 import argparse
@@ -53,10 +53,10 @@ def parse_args():
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--random-weights", action="store_true",
                    help="file inputs with the hash-seeded random initialisation instead of the checkpoints of --config")
-    p.add_argument("--format", default="gif", choices=["gif", "npy", "avi", "apng", "pngs"],
+    p.add_argument("--format", default="gif", choices=["gif", "npy", "avi", "apng", "pngs", "webp"],
                    help="output container of the file-input mode; avi = Motion-JPEG encoded on the device; apng = lossless animated PNG, pngs = a "
-                        "directory of 0000.png, 0001.png, ..., both filtered and deflated on the device (mmgt_amd.video_out); with --synthetic, "
-                        "apng / pngs also write the clip that way")
+                        "directory of 0000.png, 0001.png, ..., both filtered and deflated on the device; webp = lossless animated WebP, predicted "
+                        "and prefix-coded on the device (mmgt_amd.video_out); with --synthetic, apng / pngs / webp also write the clip that way")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
@@ -315,6 +315,11 @@ def main():
         extra["apng"] = os.path.splitext(path)[0] + ".apng"
         save_videos_grid(v, extra["apng"], n_rows=1, fps=a.fps)
         extra["apng_bytes"] = os.path.getsize(extra["apng"])
+    if a.format == "webp" and not a.no_decode:
+        from mmgt_amd.video_out import save_videos_grid
+        extra["webp"] = os.path.splitext(path)[0] + ".webp"
+        save_videos_grid(v, extra["webp"], n_rows=1, fps=a.fps)
+        extra["webp_bytes"] = os.path.getsize(extra["webp"])
     if a.format == "pngs" and not a.no_decode:
         from mmgt_amd.video_out import encode_png_frames, frames_uint8, write_png_sequence
         extra["pngs"] = os.path.splitext(path)[0] + "_png"
