@@ -538,6 +538,31 @@ int mmgt_gif_unlzw(const unsigned char* data, long long data_bytes, const long l
  * the canvas or whose indices leave idx_bytes draws nothing. */
 int mmgt_gif_compose(const long long* tab, const unsigned char* idx, long long idx_bytes, const unsigned char* palette, unsigned char* carry,
                      unsigned char* out, int n, int H, int W, void* stream);
+/* ---- WebP lossless input path (csrc/webpdec.hip, csrc/webpdec_core.h, mmgt_amd/video_in.py): a set of n frames (VP8L streams) of one or
+ * more files of one canvas size.  Every buffer is a device pointer; the status words are those of csrc/webpdec_core.h (0: fine).  tab (n, 16) long
+ * long is one row per frame (webpdec_core.h: WD_X .. WD_PH): rectangle on the canvas, the stream's byte range in data, offset and count of its
+ * scratch words, offset of its ARGB words, flags (1 blend, 2 key frame, 4 first frame of its file, 8 the frame before disposes to background) and
+ * that earlier frame's rectangle.  Arguments outside the stated range: non-zero, nothing launched, mmgt_last_error() says "range".
+ * decode: frame f's VP8L stream data[tab[f].begin .. tab[f].end) (data_bytes a positive multiple of 16 that covers every stream, data and scratch
+ * 16-byte aligned; 1 <= n <= 65535) -> its scratch words scratch[tab[f].scr .. + tab[f].cap): a header block of 32 words (the transforms in the
+ * order read), the sub-images, the prefix-code groups where there are several, and the entropy-coded main image; and status[f].  Nothing is
+ * written outside those words; a row that names bytes or words outside the buffers gives status 12 and touches nothing.  A frame whose
+ * prefix-code groups (known only once its entropy image is decoded) do not fit its scratch words gives a NEGATIVE status: minus the words with
+ * which it decodes, for the caller to come again.  One 64-thread workgroup per stream; every round of its loops consumes a bit, produces a pixel
+ * or stops. */
+int mmgt_webp_decode(const unsigned char* data, long long data_bytes, const long long* tab, unsigned int* scratch, long long scratch_words, int* status,
+                     int n, void* stream);
+/* untransform: each frame's transforms undone in its own order (frames of one call may differ in them) -> the ARGB words (A in the high byte) of its
+ * own rectangle, W * H of them at argb + tab[f].pix, and status[f]; a frame whose decode left no valid header block gives status 13 and writes
+ * nothing.  The scratch words are used up.  One 64-thread workgroup per frame. */
+int mmgt_webp_untransform(const long long* tab, unsigned int* scratch, long long scratch_words, unsigned int* argb, long long argb_words, int* status,
+                          int n, void* stream);
+/* compose: the call's frames drawn in order on the H x W canvas (sides 1 .. 16384, 1 <= n <= 65535) as libwebp's WebPAnimDecoder composes them
+ * -> out (n, H, W, 3) u8 RGB.  carry (H, W) words holds the RGBA canvas (R in the low byte): read unless tab[0] is its file's first frame, written
+ * at the end, so that a file may be decoded in several sets of launches.  A row whose rectangle leaves the canvas or whose words leave argb_words
+ * draws nothing. */
+int mmgt_webp_compose(const long long* tab, const unsigned int* argb, long long argb_words, unsigned int* carry, unsigned char* out, int n, int H, int W,
+                      void* stream);
 /* SMGA key points -> the four frame streams of Stage 2, drawn on the device: kp (frames, 134, 3) fp32 = SMGA's normalised
  * (x, y, score) features.  Replaces data/extract_movment_mask_all.py:319-321 `pose_vid_generator` (denormalize :128-132, mask_leg :66-89,
  * process_keypoints :98-119), src/dwpose/__init__.py:220-283 `DWposeDetector_movment_mask.__call__` with draw_pose / draw_pose_mask_head /

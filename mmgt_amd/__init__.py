@@ -14,7 +14,7 @@ def __getattr__(name):
         from . import wavlm
         return getattr(wavlm, name)
     if name in ("parse_jpeg", "decode_jpeg_frames", "parse_png", "decode_png_frames", "parse_gif", "decode_gif_frames",
-                "read_frames_device"):
+                "parse_webp", "decode_webp_frames", "read_frames_device"):
         from . import video_in
         return getattr(video_in, name)
     if name in ("pose_tensor_device", "motion_masks_device", "resize_frames_device", "ref_image_tensors_device"):

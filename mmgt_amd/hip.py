@@ -138,6 +138,9 @@ _SIGS = {
     "mmgt_png_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_unlzw": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
     "mmgt_gif_compose": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_webp_decode": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
+    "mmgt_webp_untransform": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
+    "mmgt_webp_compose": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
@@ -1573,6 +1576,70 @@ def gif_compose(tab, idx, palette, carry, H, W, out=None):
     if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous() or out.device != idx.device:
         raise RuntimeError(f"gif_compose: out must be contiguous uint8 ({n}, {H}, {W}, 3) on {idx.device}")
     _check(lib().mmgt_gif_compose(_ptr(tab), _ptr(idx), idx.numel(), _ptr(palette), _ptr(carry), _ptr(out), n, H, W, _stream()), "mmgt_gif_compose")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ WebP lossless input (csrc/webpdec.hip)
+
+WEBPDEC_TAB = 16                    # long long words per frame row (csrc/webpdec_core.h: WD_TAB)
+WEBPDEC_GROUP_WORDS = 14768 // 4    # scratch words of one prefix-code group (csrc/webpdec_core.h: sizeof(WdGroup) / 4)
+
+
+def _webp_tab(tab, what):
+    if tab.dtype != torch.int64 or tab.dim() != 2 or tab.shape[1] != WEBPDEC_TAB or tab.shape[0] < 1 or not tab.is_contiguous():
+        raise RuntimeError(f"{what}: expected tab int64 (n, {WEBPDEC_TAB}), n >= 1, contiguous")
+    return tab.shape[0]
+
+
+def _webp_words(t, name, what):
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() < 1 or not t.is_contiguous():
+        raise RuntimeError(f"{what}: expected {name} int32 (words,), contiguous")
+
+
+def webp_decode(data, tab, scratch, out=None):
+    """The VP8L streams of n frames (data uint8, a multiple of 16 bytes; tab int64 (n, 16), one row per frame: include/mmgt_hip.h) -> every frame's
+    scratch words (header block, sub-images, entropy-coded main image) in scratch int32 (words,) at its row's offset, and status (n,) int32, which
+    is returned (negative: minus the scratch words the frame needs for its prefix-code groups).  `out`: the status tensor to write into."""
+    _dev(data, tab, scratch)
+    n = _webp_tab(tab, "webp_decode")
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise RuntimeError("webp_decode: expected data uint8 (bytes,), contiguous")
+    _webp_words(scratch, "scratch", "webp_decode")
+    status = _status_words(out, n, data.device, "webp_decode")
+    _check(lib().mmgt_webp_decode(_ptr(data), data.numel(), _ptr(tab), _ptr(scratch), scratch.numel(), _ptr(status), n, _stream()), "mmgt_webp_decode")
+    return status
+
+
+def webp_untransform(tab, scratch, argb_words=None, out=None):
+    """Every frame's transforms undone in its own order: scratch as webp_decode left it (it is used up) -> (argb int32 (words,): the ARGB words of
+    each frame's own rectangle at its row's offset, status (n,) int32).  `out` = (argb, status) to write into, either may be None; without an argb
+    tensor, argb_words says how many words to allocate."""
+    _dev(tab, scratch)
+    n = _webp_tab(tab, "webp_untransform")
+    _webp_words(scratch, "scratch", "webp_untransform")
+    argb, status = out if out is not None else (None, None)
+    if argb is None:
+        argb = torch.empty((int(argb_words),), device=scratch.device, dtype=torch.int32)
+    _webp_words(argb, "argb", "webp_untransform")
+    status = _status_words(status, n, scratch.device, "webp_untransform")
+    _check(lib().mmgt_webp_untransform(_ptr(tab), _ptr(scratch), scratch.numel(), _ptr(argb), argb.numel(), _ptr(status), n, _stream()),
+           "mmgt_webp_untransform")
+    return argb, status
+
+
+def webp_compose(tab, argb, carry, H, W, out=None):
+    """The call's frames composed on the H x W canvas: tab int64 (n, 16), argb int32 (words,) as webp_untransform wrote it, carry int32 (H, W), the
+    RGBA canvas (read unless tab[0] is its file's first frame, written at the end) -> (n, H, W, 3) uint8 RGB.  `out`: a tensor to write into."""
+    _dev(tab, argb, carry)
+    n, H, W = _webp_tab(tab, "webp_compose"), int(H), int(W)
+    _webp_words(argb, "argb", "webp_compose")
+    if carry.dtype != torch.int32 or tuple(carry.shape) != (H, W) or not carry.is_contiguous():
+        raise RuntimeError(f"webp_compose: expected carry int32 ({H}, {W}), contiguous")
+    if out is None:
+        out = torch.empty((n, H, W, 3), device=argb.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous() or out.device != argb.device:
+        raise RuntimeError(f"webp_compose: out must be contiguous uint8 ({n}, {H}, {W}, 3) on {argb.device}")
+    _check(lib().mmgt_webp_compose(_ptr(tab), _ptr(argb), argb.numel(), _ptr(carry), _ptr(out), n, H, W, _stream()), "mmgt_webp_compose")
     return out
 
 

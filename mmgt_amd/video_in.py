@@ -13,8 +13,14 @@
                        
   decode_gif_frames    one GIF file -> (n, H, W, 3) uint8 RGB on the device: un-LZW, de-interlace and PIL's frame composition (sub-rectangles, local
                        palettes, transparency, the four disposals) run in csrc/gifdec.hip, byte for byte ImageSequence.Iterator + convert("RGB")
-  read_frames_device   a Motion-JPEG .avi, a directory of .jpg frames, a directory of .png frames, one .png / .apng file (animated or not) or one
-                       .gif file -> the same tensor; anything else raises (inputs.read_frames is the host route)
+  parse_webp           the chunks of one lossless WebP file, still or animated -> WebpHeader (canvas, loop count, and per frame the rectangle,
+                       duration, blend, dispose, alpha flag, key-frame flag and VP8L payload); refuses on the host, with a ValueError naming the
+                       cause, what the kernels do not decode
+  decode_webp_frames   lossless WebP files of one canvas size -> (n, H, W, 3) uint8 RGB on the device: the VP8L entropy decode, the inverse
+                       transforms and libwebp's frame composition run in csrc/webpdec.hip, byte for byte ImageSequence.Iterator + convert("RGB")
+  read_frames_device   a Motion-JPEG .avi, a directory of .jpg frames, a directory of .png frames, a directory of .webp frames, one .png / .apng
+                       file (animated or not), one .gif file or one .webp file (animated or not) -> the same tensor; anything else raises
+                       (inputs.read_frames is the host route)
 """
 from dataclasses import dataclass, field
 from pathlib import Path
@@ -747,12 +753,250 @@ def decode_gif_frames(data, device="cuda", out=None, limit=None):
         raise RuntimeError(f"decode_gif_frames: frame {f}, image data: {GIF_STATUS_TEXT.get(int(st[f]), f'status {int(st[f])}')}")
     return out
 
+# ---------------------------------------------------------------------------------------------------------------- WebP lossless
+
+WEBPDEC_SCRATCH_BYTES = 256 << 20   # decode_webp_frames holds at most this much scratch and ARGB words per set of launches (one frame at least)
+WEBPDEC_GROUP_BYTES = 1 << 20       # of a frame's scratch, at most this much is set aside AT FIRST for prefix-code groups beyond the first; a frame
+                                    # that needs more says how much, and the call is run again with exactly that
+WEBP_MAX_SIDE = 16384
+
+# csrc/webpdec_core.h's status words
+WEBP_STATUS_TEXT = {1: "a VP8L signature other than 0x2f or a version other than 0", 2: "a VP8L size that differs from the frame's rectangle",
+                    3: "a transform read twice", 4: "a prefix code that is over-subscribed, incomplete or empty",
+                    5: "a symbol outside its alphabet, or bits that are no code", 6: "a code-length repeat or max_symbol past the alphabet",
+                    7: "colour-cache bits outside 1 .. 11", 8: "a distance beyond the pixels produced", 9: "a copy that runs past the image",
+                    10: "data exhausted before the last pixel", 11: "more sub-images or prefix-code groups than the frame's scratch holds",
+                    12: "a frame descriptor outside the batch", 13: "no decoded image to undo the transforms of"}
+
+# csrc/webpdec_core.h's table row (checked against the binding's WEBPDEC_TAB on every call)
+_WD_X, _WD_Y, _WD_W, _WD_H, _WD_BEGIN, _WD_END, _WD_SCR, _WD_CAP, _WD_PIX, _WD_FLAGS, _WD_PX, _WD_PY, _WD_PW, _WD_PH = range(14)
+_WD_BLEND, _WD_KEY, _WD_FIRST, _WD_PREV_DISPOSED = 1, 2, 4, 8
+WEBP_TAB = 16
+_WD_HDR_WORDS = 32
+
+
+@dataclass
+class WebpFrame:
+    x: int
+    y: int
+    width: int
+    height: int
+    duration: int                                # milliseconds; 0 for a still
+    blend: bool                                  # ANMF flag bit 1 clear
+    dispose: bool                                # ANMF flag bit 0: the rectangle is zeroed before the next frame draws
+    alpha_is_used: bool                          # the VP8L header's bit
+    key: bool                                    # libwebp's key frame: the canvas is zeroed before it draws, and it does not blend
+    payload: bytes                               # the VP8L chunk's body
+
+
+@dataclass
+class WebpHeader:
+    width: int                                   # the canvas
+    height: int
+    loop: int
+    animated: bool
+    frames: List[WebpFrame] = field(default_factory=list)
+
+
+def _vp8l_header(payload, what):
+    if len(payload) < 5:
+        raise ValueError(f"parse_webp: the VP8L chunk of {what} holds {len(payload)} bytes: no room for its header")
+    v = int.from_bytes(payload[:5], "little")
+    if v & 255 != 0x2F:
+        raise ValueError(f"parse_webp: bad VP8L signature {v & 255:#04x} in {what} (0x2f)")
+    if v >> 37 & 7:
+        raise ValueError(f"parse_webp: bad VP8L version {v >> 37 & 7} in {what} (0)")
+    return (v >> 8 & 0x3FFF) + 1, (v >> 22 & 0x3FFF) + 1, bool(v >> 36 & 1)
+
+
+def parse_webp(data) -> WebpHeader:
+    """One lossless WebP file (bytes), still or animated -> WebpHeader.  ICCP, EXIF, XMP and unknown chunks are skipped, bytes behind the RIFF size
+    are ignored.  ValueError for everything outside the decoder's scope: not a RIFF/WEBP file, a RIFF size or a chunk that runs past the file, a
+    lossy `VP8 ` or an ALPH chunk, a VP8L signature other than 0x2f or a version other than 0, a frame whose VP8L size differs from its ANMF size,
+    a frame rectangle that leaves the canvas, a VP8X canvas that differs from a still's VP8L size, image data on the wrong side of the VP8X
+    animation flag, frames without an ANIM chunk before them, a canvas above 16384 a side, no frames."""
+    data = bytes(data)
+    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WEBP":
+        raise ValueError("parse_webp: not a RIFF/WEBP file")
+    end = 8 + int.from_bytes(data[4:8], "little")
+    if end > len(data):
+        raise ValueError(f"parse_webp: the RIFF size ({end - 8}) runs past the end of the file ({len(data)} bytes)")
+
+    def chunks(pos, stop, where):
+        while pos < stop:
+            if pos + 8 > stop:
+                raise ValueError(f"parse_webp: a chunk header at byte {pos} runs past the end of {where}")
+            kind, ln = data[pos:pos + 4], int.from_bytes(data[pos + 4:pos + 8], "little")
+            if pos + 8 + ln > stop:
+                raise ValueError(f"parse_webp: chunk {kind!r} at byte {pos} runs past the end of {where}")
+            if kind in (b"VP8 ", b"ALPH"):
+                raise ValueError(f"parse_webp: lossy WebP (VP8) is not decoded (chunk {kind!r} at byte {pos}; VP8L only)")
+            yield kind, pos + 8, ln
+            pos += 8 + ln + (ln & 1)
+
+    u24 = lambda at: int.from_bytes(data[at:at + 3], "little")
+    canvas, flags, loop, stills, frames = None, 0, None, [], []
+    for kind, at, ln in chunks(12, end, "the file"):
+        if kind == b"VP8X":
+            if ln < 10 or canvas is not None or stills or frames:
+                raise ValueError("parse_webp: bad VP8X chunk (its length or place)")
+            flags, canvas = data[at], (u24(at + 4) + 1, u24(at + 7) + 1)
+        elif kind == b"ANIM":
+            if ln < 6 or canvas is None or frames:
+                raise ValueError("parse_webp: bad ANIM chunk (its length or place)")
+            loop = int.from_bytes(data[at + 4:at + 6], "little")
+        elif kind == b"VP8L":
+            stills.append(data[at:at + ln])
+        elif kind == b"ANMF":
+            k = len(frames)
+            if loop is None:
+                raise ValueError("parse_webp: an ANMF chunk before any ANIM chunk")
+            if ln < 16:
+                raise ValueError(f"parse_webp: the ANMF chunk of frame {k} holds {ln} bytes: no room for its header")
+            payload = None
+            for sub, sat, sln in chunks(at + 16, at + ln, f"the ANMF chunk of frame {k}"):
+                if sub == b"VP8L" and payload is None:
+                    payload = data[sat:sat + sln]
+            if payload is None:
+                raise ValueError(f"parse_webp: frame {k} has no VP8L chunk")
+            w, h, alpha = _vp8l_header(payload, f"frame {k}")
+            x, y, fw, fh = 2 * u24(at), 2 * u24(at + 3), u24(at + 6) + 1, u24(at + 9) + 1
+            if (w, h) != (fw, fh):
+                raise ValueError(f"parse_webp: the VP8L size of frame {k} ({w} x {h}) differs from its ANMF size ({fw} x {fh})")
+            frames.append(WebpFrame(x, y, w, h, u24(at + 12), not data[at + 15] & 2, bool(data[at + 15] & 1), alpha, False, payload))
+        # ICCP, EXIF, XMP and unknown chunks: skipped
+    animated = bool(flags & 2)
+    if (frames and not animated) or (stills and animated):
+        raise ValueError("parse_webp: image data on the wrong side of the VP8X animation flag (ANMF without it, or VP8L beside it)")
+    if len(stills) > 1:
+        raise ValueError("parse_webp: more than one VP8L chunk in a still")
+    if stills:
+        w, h, alpha = _vp8l_header(stills[0], "the still")
+        if canvas is not None and canvas != (w, h):
+            raise ValueError(f"parse_webp: the VP8X canvas ({canvas[0]} x {canvas[1]}) differs from the still's VP8L size ({w} x {h})")
+        canvas = (w, h)
+        frames = [WebpFrame(0, 0, w, h, 0, False, False, alpha, True, stills[0])]
+    if not frames:
+        raise ValueError("parse_webp: no frames")
+    W, H = canvas
+    if W > WEBP_MAX_SIDE or H > WEBP_MAX_SIDE:
+        raise ValueError(f"parse_webp: a canvas is 1 .. {WEBP_MAX_SIDE} pixels a side, got {W} x {H}")
+    for k, f in enumerate(frames):
+        if f.x + f.width > W or f.y + f.height > H:
+            raise ValueError(f"parse_webp: the rectangle of frame {k} ({f.width} x {f.height} at ({f.x}, {f.y})) leaves the canvas ({W} x {H})")
+        covers = (f.x, f.y, f.width, f.height) == (0, 0, W, H)
+        before = frames[k - 1] if k else None
+        f.key = (k == 0 or (covers and (not f.alpha_is_used or not f.blend))
+                 or (before.dispose and (before.key or (before.x, before.y, before.width, before.height) == (0, 0, W, H))))
+    return WebpHeader(W, H, loop or 0, animated, frames)
+
+
+def webp_frame_scratch_words(f: WebpFrame) -> int:
+    """Scratch words of one frame as first given: the header block, the main image, three sub-images at the finest block size (predictor,
+    cross-colour, entropy image), a palette, and room for the prefix-code groups beyond the first: no more of them than entropy-image pixels or
+    than the payload has bits for (a group's five codes take 20 bits at least), and no more than WEBPDEC_GROUP_BYTES.  The number of groups is
+    known only once the entropy image is decoded: a frame with more than fit here ends with minus the words it needs as its status."""
+    from . import hip
+    sub = -(-f.width // 4) * -(-f.height // 4)
+    groups = min(sub, 8 * len(f.payload) // 20)
+    area = min(groups * hip.WEBPDEC_GROUP_WORDS, WEBPDEC_GROUP_BYTES // 4) if groups > 1 else 0
+    return (_WD_HDR_WORDS + f.width * f.height + 3 * sub + 256 + 32 + area + 3) & ~3
+
+
+def webp_operands(headers, limit: Optional[int] = None, scratch_bytes: Optional[int] = None, caps: Optional[Dict[int, int]] = None):
+    """Host-side operands of one decode: (tab int64 (n, 16), data uint8 (bytes,) padded to a multiple of 16, chunks [(f0, f1, scratch words, ARGB
+    words)]).  n = the files' first `limit` frames in order; the chunks are runs of frames whose scratch and ARGB words together fit scratch_bytes
+    (one frame at least), and a row's offsets count from its chunk's start.  caps: frame -> the scratch words it asked for in an earlier run."""
+    if not headers:
+        raise ValueError("decode_webp_frames: no frames")
+    for k, h in enumerate(headers):
+        if (h.width, h.height) != (headers[0].width, headers[0].height):
+            raise ValueError(f"decode_webp_frames: file {k} has a canvas of {h.width} x {h.height}; file 0 has {headers[0].width} x "
+                             f"{headers[0].height}: one call decodes one canvas size")
+    frames = [(f, k == 0, h.frames[k - 1] if k else None) for h in headers for k, f in enumerate(h.frames)]
+    frames = frames if limit is None else frames[:max(0, int(limit))]
+    if not frames:
+        raise ValueError("decode_webp_frames: no frames")
+    budget = (WEBPDEC_SCRATCH_BYTES if scratch_bytes is None else int(scratch_bytes)) // 4
+    tab = np.zeros((len(frames), WEBP_TAB), np.int64)
+    chunks, begin, f0, scr, pix = [], 0, 0, 0, 0
+    for k, (f, first, before) in enumerate(frames):
+        cap, npix = max(webp_frame_scratch_words(f), ((caps or {}).get(k, 0) + 3) & ~3), f.width * f.height
+        if k > f0 and scr + cap + pix + npix > budget:
+            chunks.append((f0, k, scr, pix))
+            f0, scr, pix = k, 0, 0
+        t = tab[k]
+        t[_WD_X], t[_WD_Y], t[_WD_W], t[_WD_H] = f.x, f.y, f.width, f.height
+        t[_WD_BEGIN], t[_WD_END], t[_WD_SCR], t[_WD_CAP], t[_WD_PIX] = begin, begin + len(f.payload), scr, cap, pix
+        t[_WD_FLAGS] = _WD_BLEND * f.blend | _WD_KEY * f.key | _WD_FIRST * first
+        if before is not None and before.dispose:
+            t[_WD_FLAGS] |= _WD_PREV_DISPOSED
+            t[_WD_PX], t[_WD_PY], t[_WD_PW], t[_WD_PH] = before.x, before.y, before.width, before.height
+        scr += cap
+        pix += npix
+        begin += len(f.payload)
+    chunks.append((f0, len(frames), scr, pix))
+    blob = b"".join(f.payload for f, _, _ in frames)
+    data = np.frombuffer(blob + bytes(16 + (-len(blob)) % 16), np.uint8)
+    return tab, data, chunks
+
+
+def decode_webp_frames(files, device="cuda", out=None, limit=None):
+    """Lossless WebP files (a list of bytes; one bytes object is a list of one), still or animated, all of one canvas size -> (n, H, W, 3) uint8
+    RGB on `device`, contiguous, n = all frames of all files in order (the first `limit` of them; later ones are neither decoded nor composed):
+    byte for byte what PIL's ImageSequence.Iterator(Image.open(f)) gives after convert("RGB") -- the whole of VP8L, and sub-rectangles, blend and
+    dispose composed as libwebp's WebPAnimDecoder composes them, anew at each file.  `out`: a tensor of that shape to write into.  Out-of-scope
+    files raise ValueError before anything is launched; a stream that does not decode raises RuntimeError naming the first bad frame and the
+    cause, and no pixels are returned.  The status words are read once per call; a frame with more prefix-code groups than its first scratch
+    allowance holds (WEBPDEC_GROUP_BYTES) says so in its status, and the call's launches are then run once more with what such frames need."""
+    if isinstance(files, (bytes, bytearray, memoryview)):
+        files = [files]
+    headers = [parse_webp(b) for b in files]
+    return _decode_webp_headers(headers, device, out, limit)
+
+
+def _decode_webp_headers(headers, device, out=None, limit=None, caps=None):
+    import torch
+    from . import hip
+    tab, blob, chunks = webp_operands(headers, limit, caps=caps)
+    if hip.WEBPDEC_TAB != WEBP_TAB:
+        raise RuntimeError(f"decode_webp_frames: the binding's table row has {hip.WEBPDEC_TAB} words, this module builds {WEBP_TAB}")
+    n, H, W = len(tab), headers[0].height, headers[0].width
+    dev = torch.device(device)
+    if out is None:
+        out = torch.empty((n, H, W, 3), device=dev, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError(f"decode_webp_frames: out must be contiguous uint8 ({n}, {H}, {W}, 3) on the device")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_data, d_tab = up(blob.copy()), up(tab)
+    status = torch.empty((2, n), device=dev, dtype=torch.int32)
+    scratch = torch.empty((max(c[2] for c in chunks),), device=dev, dtype=torch.int32)
+    argb = torch.empty((max(c[3] for c in chunks),), device=dev, dtype=torch.int32)
+    carry = torch.empty((H, W), device=dev, dtype=torch.int32)                # the RGBA canvas, from one chunk to the next
+    for f0, f1, scr_words, argb_words in chunks:
+        hip.webp_decode(d_data, d_tab[f0:f1], scratch[:scr_words], out=status[0, f0:f1])
+        hip.webp_untransform(d_tab[f0:f1], scratch[:scr_words], out=(argb[:argb_words], status[1, f0:f1]))
+        hip.webp_compose(d_tab[f0:f1], argb[:argb_words], carry, H, W, out=out[f0:f1])
+    st = status.cpu().numpy()                                                  # the one read of the status words (it also orders the launches)
+    bad = np.flatnonzero(st[0])
+    if bad.size and st[0, bad[0]] < 0 and caps is None:                        # more groups than the first allowance: once more, with what they need
+        del scratch, argb, carry
+        return _decode_webp_headers(headers, device, out, limit, {int(f): -int(st[0, f]) for f in np.flatnonzero(st[0] < 0)})
+    for stage, name in ((0, "image data"), (1, "transforms")):
+        bad = np.flatnonzero(st[stage])
+        if bad.size:
+            f = int(bad[0])
+            code = 11 if st[stage, f] < 0 else int(st[stage, f])
+            raise RuntimeError(f"decode_webp_frames: frame {f}, {name}: {WEBP_STATUS_TEXT.get(code, f'status {code}')}")
+    return out
+
 
 def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
     """(L, H, W, 3) uint8 RGB frames of `path` on `device`, decoded there: a Motion-JPEG .avi (what video_out.write_avi writes, or any stock
-    tool's `-c:v mjpeg`), a directory whose images are all .jpg / .jpeg or all .png (sorted by name; a .png file gives its first frame), one
-    .png / .apng file, animated or not (what video_out.write_apng / write_png write), or one .gif file (what video_out.write_gif or PIL writes).
-    Everything else raises: inputs.read_frames is the host route, and the caller chooses it."""
+    tool's `-c:v mjpeg`), a directory whose images are all .jpg / .jpeg, all .png or all .webp (sorted by name; a .png or .webp file gives its
+    first frame), one .png / .apng file, animated or not (what video_out.write_apng / write_png write), one .gif file (what video_out.write_gif
+    or PIL writes), or one lossless .webp file, animated or not (what video_out.write_webp or PIL's lossless=True writes).  Everything else
+    raises: inputs.read_frames is the host route, and the caller chooses it."""
     from .inputs import IMAGE_SUFFIXES, mjpeg_avi_frames
     p = Path(path)
     if not p.exists():
@@ -764,9 +1008,18 @@ def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
             for h in heads:                                                   # a file of a directory is one frame, as for inputs.read_frames
                 h.streams, h.adlers = h.streams[:1], h.adlers[:1]
             return _decode_png_operands(png_batch_operands(None, heads), device)
+        if {f.suffix.lower() for f in files} == {".webp"}:
+            heads = [parse_webp(f.read_bytes()) for f in (files if limit is None else files[:limit])]
+            for h in heads:                                                   # a file of a directory is one frame, as for inputs.read_frames
+                h.frames = h.frames[:1]
+            if not heads:
+                raise RuntimeError(f"read_frames_device: no frames in {p}")
+            if len({(h.width, h.height) for h in heads}) > 1:
+                raise RuntimeError(f"read_frames_device: the .webp frames of {p} differ in size; use inputs.read_frames for such a directory")
+            return _decode_webp_headers(heads, device)
         other = [f.name for f in files if f.suffix.lower() not in (".jpg", ".jpeg")]
         if not files or other:
-            raise RuntimeError(f"read_frames_device: {p} must hold .jpg / .jpeg frames only, or .png frames only "
+            raise RuntimeError(f"read_frames_device: {p} must hold .jpg / .jpeg frames only, .png frames only or .webp frames only "
                                f"({'found ' + other[0] if other else 'no images'}); use inputs.read_frames for other inputs")
         jpegs = [f.read_bytes() for f in (files if limit is None else files[:limit])]
     elif p.suffix.lower() in (".png", ".apng"):
@@ -780,11 +1033,15 @@ def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
         if limit is not None and limit < 1:
             raise RuntimeError(f"read_frames_device: no frames in {p}")
         return decode_gif_frames(p.read_bytes(), device, limit=limit)
+    elif p.suffix.lower() == ".webp":
+        if limit is not None and limit < 1:
+            raise RuntimeError(f"read_frames_device: no frames in {p}")
+        return decode_webp_frames(p.read_bytes(), device, limit=limit)
     else:
         jpegs = mjpeg_avi_frames(p, limit) if p.suffix.lower() == ".avi" else None
         if jpegs is None:
-            raise RuntimeError(f"read_frames_device: {p.name} is neither a Motion-JPEG .avi, a .png / .apng file, a .gif file nor a directory of "
-                               ".jpg or .png frames; use inputs.read_frames for other inputs")
+            raise RuntimeError(f"read_frames_device: {p.name} is neither a Motion-JPEG .avi, a .png / .apng file, a .webp file, a .gif file nor a "
+                               "directory of .jpg, .png or .webp frames; use inputs.read_frames for other inputs")
     if not jpegs:
         raise RuntimeError(f"read_frames_device: no frames in {p}")
     return decode_jpeg_frames(jpegs, device)

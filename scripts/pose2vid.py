@@ -12,8 +12,8 @@ pose / mask / audio inputs, everything a pure function of names (mmgt_amd/synthe
 Without --synthetic the inputs are FILES, as in the reference (scripts/pose2vid.py:196-271): the reference image through PIL, the
 pose / mask clips as directories of images, .npy stacks or animated images (mmgt_amd/inputs.py: video containers need PyAV / cv2,
 which this build does not include, and say so), the masks blurred / resampled on the device (mmgt_amd/conditioning.py).  --decoder device
-reads Motion-JPEG .avi clips, directories of .jpg or .png frames, .png / .apng files or .gif files on the GPU instead (mmgt_amd/video_in.py,
-DESIGN 4e, 4h, 4i) and runs the
+reads Motion-JPEG .avi clips, directories of .jpg, .png or lossless .webp frames, .png / .apng files, .gif files or lossless .webp files on the
+GPU instead (mmgt_amd/video_in.py) and runs the
 resizes of the pose frames and of the reference image there too (PIL's resampling, byte for byte: DESIGN 4f).  Weights
 come from the checkpoints the config yaml names (:137-190) -- or, with --random-weights, from the hash-seeded initialisation (no
 checkpoint exists in this image).  The clip is written as .gif / .npy / Motion-JPEG .avi / lossless .apng, a directory of .png files or lossless animated .webp (mp4 muxing is out of scope:
@@ -63,8 +63,9 @@ def parse_args():
                         "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
     p.add_argument("--decoder", default="pil", choices=["pil", "device"],
                    help="how --pose_path and the mask paths are read: pil = on the host (any input read_frames takes); device = Motion-JPEG "
-                        ".avi, a directory of .jpg or of .png frames, a .png / .apng file or a .gif file, decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
-                        "resized on the device too (a baseline .jpg or a .png is also decoded there)")
+                        ".avi, a directory of .jpg, of .png or of lossless .webp frames, a .png / .apng file, a .gif file or a lossless .webp file (animated or "
+                        "not), decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
+                        "resized on the device too (a baseline .jpg, a .png or a lossless .webp is also decoded there)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -150,7 +151,7 @@ def build_from_checkpoints(cfg_path, num_c, dev, dtype):
 
 def load_inputs(a, dev):
     """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG,
-    PNG / APNG and GIF on the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
+    PNG / APNG, GIF and lossless WebP on the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
     from mmgt_amd import inputs
     device = getattr(a, "decoder", "pil") == "device"
     if device:
@@ -178,18 +179,20 @@ def load_inputs(a, dev):
 
 def load_ref_image(a, dev):
     """The reference image as the pipeline takes it: a PIL image, or with --decoder device a uint8 (h, w, 3) tensor on the device -- a baseline
-    .jpg or a .png is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
+    .jpg, a .png or a lossless .webp (its first frame) is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
     from PIL import Image
     if getattr(a, "decoder", "pil") != "device":
         return Image.open(a.image_path).convert("RGB")
     suffix = os.path.splitext(a.image_path)[1].lower()
-    if suffix in (".jpg", ".jpeg", ".png"):
-        from mmgt_amd.video_in import decode_jpeg_frames, decode_png_frames
+    if suffix in (".jpg", ".jpeg", ".png", ".webp"):
+        from mmgt_amd.video_in import decode_jpeg_frames, decode_png_frames, decode_webp_frames
         with open(a.image_path, "rb") as fh:
             data = fh.read()
         try:
+            if suffix == ".webp":
+                return decode_webp_frames([data], dev, limit=1)[0]
             return (decode_png_frames if suffix == ".png" else decode_jpeg_frames)([data], dev)[0]
-        except ValueError as e:                                  # outside the device decoders' scope (progressive, CMYK, 16 bit, interlace, ...): the parser says why
+        except ValueError as e:                                  # outside the device decoders' scope (progressive, CMYK, 16 bit, interlace, lossy WebP, ...): the parser says why
             print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
     import numpy as np
     return torch.from_numpy(np.asarray(Image.open(a.image_path).convert("RGB")).copy()).to(dev)
