@@ -504,6 +504,30 @@ int mmgt_webp_histogram(const unsigned int* res, unsigned int* hist, int n, long
 int mmgt_webp_code(const unsigned int* res, const unsigned int* codes, const unsigned int* header, const long long* header_off, long long header_words,
                    unsigned int* slots, const long long* slot_off, long long slots_words, long long* bits, int n, long long frame_px,
                    long long strip_px, void* stream);
+/* ---- WebP lossy output path (csrc/vp8.hip, csrc/vp8_core.h, mmgt_amd/video_out.py): one VP8 key frame per RGB frame.  Every buffer is a
+ * device pointer unless said otherwise.  Like every entry: 0 on success, else mmgt_last_error() has the text and nothing was launched.  With
+ * mbh = ceil(H / 16), mbw = ceil(W / 16): n, H, W >= 1, H, W <= 16383, n * mbh * mbw < 2^25; q = the quantiser index 0 .. 127; partitions 1, 2, 4, 8.
+ * quantiser: (host pointers) quality 0 .. 100 -> its quantiser index and the default loop filter level of that index.
+ * slot_bytes: (host pointers) the worst-case bytes of a first partition and of a token partition (DESIGN 4l derives them).
+ * convert: frames (n, H, W, 3) u8 RGB -> Y (n, 16 mbh, 16 mbw), U, V (n, 8 mbh, 8 mbw), studio range, the frame padded by edge replication.
+ * analyse: predicts (16 x 16 and chroma modes 0 DC, 1 V, 2 H, 3 TM; smallest squared error against the source, the lower mode on a tie), transforms,
+ * quantises and reconstructs every macroblock: levels (n, mbh, mbw, 25, 16) int16 in scan order (blocks 0 .. 15 luma, 16 .. 19 U, 20 .. 23 V, 24 Y2),
+ * modes (n, mbh, mbw, 2), nz (n, mbh, mbw) masks of the blocks with a non-zero level, skipped (n) = macroblocks whose mask is 0, and the reconstructed
+ * planes ry, ru, rv shaped like Y, U, V.  One workgroup per frame; no workgroup waits for another.
+ * code: per frame the first partition (header fields, skip flags, modes) and `partitions` token partitions (macroblock row r in partition
+ * r mod partitions), each by a boolean coder of its own into its slot: frame f's slots start at f * (first + partitions * token) bytes of slots, the
+ * first partition's, then the token partitions'.  counts (n, 1 + partitions) = each coder's bytes, -1 if its slot was too small.
+ * pack: frame f's payload (frame tag, start code, sizes, first partition, partitions - 1 sizes of 3 bytes, partitions) -> out[out_off[f] ..
+ * out_off[f + 1]) (out_off has n + 1 entries; 10 + 3 * (partitions - 1) + the frame's counts bytes each).  Nothing outside out_bytes is written. */
+int mmgt_vp8_quantiser(int quality, int* q, int* filter_level);
+int mmgt_vp8_slot_bytes(int H, int W, int partitions, long long* first_bytes, long long* token_bytes);
+int mmgt_vp8_convert(const unsigned char* frames, unsigned char* Y, unsigned char* U, unsigned char* V, int n, int H, int W, void* stream);
+int mmgt_vp8_analyse(const unsigned char* Y, const unsigned char* U, const unsigned char* V, unsigned char* ry, unsigned char* ru, unsigned char* rv,
+                     short* levels, unsigned char* modes, unsigned int* nz, int* skipped, int n, int H, int W, int q, void* stream);
+int mmgt_vp8_code(const short* levels, const unsigned int* nz, const unsigned char* modes, const int* skipped, unsigned char* slots,
+                  long long slots_bytes, long long* counts, int n, int H, int W, int q, int partitions, int filter_level, void* stream);
+int mmgt_vp8_pack(const unsigned char* slots, long long slots_bytes, const long long* counts, unsigned char* out, const long long* out_off,
+                  long long out_bytes, int n, int H, int W, int partitions, void* stream);
 /* ---- PNG input path (csrc/pngdec.hip, csrc/pngdec_core.h, mmgt_amd/video_in.py): non-interlaced PNG / APNG frames of one geometry.  Every
  * buffer is a device pointer; the status words are those of csrc/pngdec_core.h (0: fine).  Arguments outside the stated range: non-zero, nothing
  * launched, mmgt_last_error() says "range".

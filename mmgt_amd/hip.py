@@ -133,6 +133,14 @@ _SIGS = {
     "mmgt_webp_histogram": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
     "mmgt_webp_code": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int,
                                ctypes.c_longlong, ctypes.c_longlong, c_void_p]),
+    "mmgt_vp8_quantiser": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "mmgt_vp8_slot_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]),
+    "mmgt_vp8_convert": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_vp8_analyse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                 c_int, c_int, c_void_p]),
+    "mmgt_vp8_code": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                              c_int, c_void_p]),
+    "mmgt_vp8_pack": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_png_inflate": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "mmgt_png_unfilter": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_png_expand": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
@@ -1447,6 +1455,114 @@ def webp_pack(slots, want_bits, out=None):
         d_off, d_bit, d_out = up(off[f0 * k:f1 * k + 1]), up(bit_off[f0:f1]), up(out_off[f0:f1 + 1])                                # alive until launched
         _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, k,
                                    _stream()), "mmgt_png_pack")
+    return out, out_off
+
+
+# ------------------------------------------------------------------------------------------------------------ WebP lossy (csrc/vp8.hip)
+
+VP8_MAX_SIDE = 16383                # V8_MAX_SIDE: the frame header's 14-bit sizes
+VP8_MB_BLOCKS = 25                  # a macroblock's blocks of 16 levels: 16 luma, 4 U, 4 V, Y2
+
+
+def vp8_quantiser(quality):
+    """quality 0 .. 100 -> (the quantiser index 0 .. 127, the default loop filter level of that index) (see mmgt_vp8_quantiser)."""
+    q, level = c_int(0), c_int(0)
+    _check(lib().mmgt_vp8_quantiser(int(quality), ctypes.byref(q), ctypes.byref(level)), "mmgt_vp8_quantiser")
+    return q.value, level.value
+
+
+def vp8_slot_bytes(H, W, partitions):
+    """(worst-case bytes of a first partition, of a token partition) of an H x W frame (see mmgt_vp8_slot_bytes)."""
+    first, token = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    _check(lib().mmgt_vp8_slot_bytes(int(H), int(W), int(partitions), ctypes.byref(first), ctypes.byref(token)), "mmgt_vp8_slot_bytes")
+    return first.value, token.value
+
+
+def _vp8_planes(n, H, W, device):
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    return tuple(torch.empty((n, s * mbh, s * mbw), device=device, dtype=torch.uint8) for s in (16, 8, 8))
+
+
+def _vp8_check_planes(planes, n, H, W, what):
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    _dev(*planes)
+    for p, s in zip(planes, (16, 8, 8)):
+        if p.shape != (n, s * mbh, s * mbw) or p.dtype != torch.uint8 or not p.is_contiguous():
+            raise RuntimeError(f"{what}: planes must be contiguous uint8 ({n}, 16 mbh, 16 mbw), ({n}, 8 mbh, 8 mbw) twice")
+
+
+def vp8_convert(frames, out=None):
+    """(n, H, W, 3) uint8 RGB -> (Y, U, V) of the frames padded to whole macroblocks (see mmgt_vp8_convert).  `out` = the planes to write into."""
+    n, H, W = _gif_frames(frames, "vp8_convert")
+    if out is None:
+        out = _vp8_planes(n, H, W, frames.device)
+    if min(n, H, W) >= 1 and max(H, W) <= VP8_MAX_SIDE:
+        _vp8_check_planes(out, n, H, W, "vp8_convert")
+    _check(lib().mmgt_vp8_convert(_ptr(frames), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), n, H, W, _stream()), "mmgt_vp8_convert")
+    return out
+
+
+def vp8_analyse(planes, H, W, q, out=None):
+    """The planes of vp8_convert -> (recon (Y, U, V), levels (n, mbh, mbw, 25, 16) int16, modes (n, mbh, mbw, 2) uint8, nz (n, mbh, mbw) int32 masks,
+    skipped (n,) int32) (see mmgt_vp8_analyse).  `out` = the same tuple to write into."""
+    n, H, W = planes[0].shape[0], int(H), int(W)
+    _vp8_check_planes(planes, n, H, W, "vp8_analyse")
+    mbh, mbw = -(-H // 16), -(-W // 16)
+    dev = planes[0].device
+    if out is None:
+        out = (_vp8_planes(n, H, W, dev), torch.empty((n, mbh, mbw, VP8_MB_BLOCKS, 16), device=dev, dtype=torch.int16),
+               torch.empty((n, mbh, mbw, 2), device=dev, dtype=torch.uint8), torch.empty((n, mbh, mbw), device=dev, dtype=torch.int32),
+               torch.empty((n,), device=dev, dtype=torch.int32))
+    recon, levels, modes, nz, skipped = out
+    _vp8_check_planes(recon, n, H, W, "vp8_analyse")
+    assert levels.shape == (n, mbh, mbw, VP8_MB_BLOCKS, 16) and levels.dtype == torch.int16 and levels.is_contiguous()
+    assert modes.shape == (n, mbh, mbw, 2) and modes.dtype == torch.uint8 and modes.is_contiguous()
+    assert nz.shape == (n, mbh, mbw) and nz.dtype == torch.int32 and nz.is_contiguous()
+    assert skipped.shape == (n,) and skipped.dtype == torch.int32 and skipped.is_contiguous()
+    _check(lib().mmgt_vp8_analyse(_ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), _ptr(recon[0]), _ptr(recon[1]), _ptr(recon[2]), _ptr(levels),
+                                  _ptr(modes), _ptr(nz), _ptr(skipped), n, H, W, int(q), _stream()), "mmgt_vp8_analyse")
+    return out
+
+
+def vp8_code(levels, nz, modes, skipped, H, W, q, partitions, filter_level, out=None):
+    """The outputs of vp8_analyse -> (slots (bytes,) uint8, counts (n, 1 + partitions) int64): every partition coded into its worst-case slot and its
+    byte count (see mmgt_vp8_code and vp8_slot_bytes for the layout).  `out` = (slots, counts) to write into."""
+    _dev(levels, nz, modes, skipped)
+    n, H, W, partitions = levels.shape[0], int(H), int(W), int(partitions)
+    per_frame = 1
+    if partitions in (1, 2, 4, 8) and min(H, W) >= 1 and max(H, W) <= VP8_MAX_SIDE:
+        first, token = vp8_slot_bytes(H, W, partitions)
+        per_frame = first + partitions * token
+    if out is None:
+        out = (torch.empty((n * per_frame,), device=levels.device, dtype=torch.uint8),
+               torch.empty((n, 1 + max(1, partitions)), device=levels.device, dtype=torch.int64))
+    slots, counts = out
+    assert slots.dim() == 1 and slots.dtype == torch.uint8 and slots.is_contiguous()
+    assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() >= n * (1 + max(1, partitions))
+    _check(lib().mmgt_vp8_code(_ptr(levels), _ptr(nz), _ptr(modes), _ptr(skipped), _ptr(slots), slots.numel(), _ptr(counts), n, H, W, int(q),
+                               partitions, int(filter_level), _stream()), "mmgt_vp8_code")
+    return slots, counts
+
+
+def vp8_pack(slots, counts, H, W, partitions, out=None):
+    """The slots and counts of vp8_code -> (packed (bytes,) uint8, out_off (n + 1,) host int64): frame f's 'VP8 ' payload is
+    packed[out_off[f]:out_off[f + 1]] (see mmgt_vp8_pack).  The counts are read back to place the frames.  `out` = packed to write into."""
+    import numpy as np
+    _dev(slots, counts)
+    partitions = int(partitions)
+    c = counts.cpu().numpy()
+    n = c.shape[0]
+    if (c < 0).any():
+        raise RuntimeError(f"vp8_pack: partition {tuple(np.argwhere(c < 0)[0])} did not fit its slot (mmgt_vp8_code)")
+    if (c[:, 0] >= 1 << 19).any():
+        raise RuntimeError(f"vp8_pack: a first partition of {int(c[:, 0].max())} bytes passes the frame tag's 19 bits")
+    out_off = np.concatenate([[0], np.cumsum(10 + 3 * (partitions - 1) + c.sum(1))]).astype(np.int64)
+    if out is None:
+        out = torch.empty((int(out_off[-1]),), device=slots.device, dtype=torch.uint8)
+    assert out.dim() == 1 and out.numel() >= int(out_off[-1]) and out.dtype == torch.uint8 and out.is_contiguous()
+    d_off = torch.from_numpy(out_off).to(slots.device)                                                                              # alive until launched
+    _check(lib().mmgt_vp8_pack(_ptr(slots), slots.numel(), _ptr(counts), _ptr(out), _ptr(d_off), out.numel(), n, int(H), int(W), partitions,
+                               _stream()), "mmgt_vp8_pack")
     return out, out_off
 
 

@@ -8,7 +8,9 @@ opt-in .gif writer: one palette for the clip (gif_palette, gif_lut), index map, 
 encode_gif_frames) and the GIF89a container here (write_gif).  .apng / .png are the lossless output: scanline filters and deflate on the device
 (csrc/png.hip; encode_png_frames), Huffman code lengths, block headers and the PNG / APNG chunks here (write_png, write_png_sequence, write_apng).
 .webp is the second lossless output, WebP lossless / animated WebP: subtract green, predictor choice and prefix coding on the device (csrc/webp.hip;
-encode_webp_frames), the five codes of a frame, its header and the RIFF chunks here (webp_prefix_code, webp_frame_header, write_webp)."""
+encode_webp_frames), the five codes of a frame, its header and the RIFF chunks here (webp_prefix_code, webp_frame_header, write_webp).
+webp_quality=Q makes the .webp lossy instead: every frame a VP8 key frame, colour conversion, intra prediction with its reconstruction loop,
+transforms, quantisers, the boolean coder and the packing on the device (csrc/vp8.hip; encode_vp8_frames), the same container with 'VP8 ' chunks."""
 import os
 import struct
 from pathlib import Path
@@ -826,6 +828,61 @@ def encode_webp_frames(frames_u8, strip_rows=None) -> list:
     return blobs
 
 
+VP8_SCRATCH_BYTES = 256 << 20       # encode_vp8_frames holds at most this much planes, levels, worst-case slots and packed frames per set of launches
+VP8_MAX_SIDE = 16383                # VP8's 14-bit sizes
+
+
+def vp8_default_partitions(H) -> int:
+    """8 token partitions when the frame has at least 8 macroblock rows, otherwise the largest of 1 / 2 / 4 that does not exceed the row count."""
+    rows = -(-int(H) // 16)
+    return 8 if rows >= 8 else 4 if rows >= 4 else 2 if rows >= 2 else 1
+
+
+def encode_vp8_frames(frames_u8, quality=75, partitions=None, filter_level=None) -> list:
+    """(n, H, W, 3) uint8 RGB frames (a CUDA tensor, or host data that is uploaded) -> n byte strings, each one frame's VP8 key frame, the payload
+    of a 'VP8 ' chunk (write_webp(..., lossy=True) puts the chunks around it).  Colour conversion, prediction, transforms, quantisation,
+    reconstruction, the boolean coder of every partition and the packing run on the device (csrc/vp8.hip); the host reads the partitions' byte counts
+    to place the frames and receives ONE buffer of finished bytes per set of launches.  quality 0 .. 100 picks the quantiser index; partitions is 1,
+    2, 4 or 8 (None: vp8_default_partitions); filter_level 0 .. 63 is the loop filter level the decoder applies (None: the default of the quantiser
+    index; 0 makes the decode equal the encoder's reconstruction).  The bytes are the same on every call; DESIGN.md 4l defines them."""
+    from . import hip
+    x = torch.as_tensor(frames_u8)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"encode_vp8_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
+    n, H, W, _ = x.shape
+    if n == 0 or H == 0 or W == 0:
+        raise ValueError(f"encode_vp8_frames: empty clip {tuple(x.shape)}")
+    if H > VP8_MAX_SIDE or W > VP8_MAX_SIDE:
+        raise ValueError(f"encode_vp8_frames: a frame is at most {VP8_MAX_SIDE} x {VP8_MAX_SIDE}, got {W} x {H}")
+    quality = int(quality)
+    if not 0 <= quality <= 100:
+        raise ValueError(f"encode_vp8_frames: quality must be 0 .. 100, got {quality}")
+    partitions = vp8_default_partitions(H) if partitions is None else int(partitions)
+    if partitions not in (1, 2, 4, 8):
+        raise ValueError(f"encode_vp8_frames: partitions must be 1, 2, 4 or 8, got {partitions}")
+    q, level = hip.vp8_quantiser(quality)
+    filter_level = level if filter_level is None else int(filter_level)
+    if not 0 <= filter_level <= 63:
+        raise ValueError(f"encode_vp8_frames: filter_level must be 0 .. 63, got {filter_level}")
+    if not x.is_cuda:
+        x = x.cuda()
+    x = x.contiguous()
+    mbs = -(-H // 16) * -(-W // 16)
+    first, token = hip.vp8_slot_bytes(H, W, partitions)
+    # source and reconstructed planes, levels, modes and masks; the worst-case slots; the packed frames are never longer than the slots
+    per_frame = 2 * 384 * mbs + (800 + 6) * mbs + 2 * (first + partitions * token) + 64
+    per_call = max(1, VP8_SCRATCH_BYTES // per_frame)
+    blobs = []
+    for f0 in range(0, n, per_call):
+        part = x[f0:f0 + per_call]
+        _, levels, modes, nz, skipped = hip.vp8_analyse(hip.vp8_convert(part), H, W, q)
+        slots, counts = hip.vp8_code(levels, nz, modes, skipped, H, W, q, partitions, filter_level)
+        packed, out_off = hip.vp8_pack(slots, counts, H, W, partitions)
+        packed = packed.cpu().numpy()
+        blobs += [packed[out_off[f]:out_off[f + 1]].tobytes() for f in range(part.shape[0])]
+    return blobs
+
+
 def _u24(v):
     return struct.pack("<I", v)[:3]
 
@@ -835,11 +892,11 @@ def webp_duration_ms(fps) -> int:
     return max(1, int(1000 / float(fps) + 0.5))
 
 
-def write_webp(path, blobs, W, H, fps, loop=0):
+def write_webp(path, blobs, W, H, fps, loop=0, lossy=False):
     """VP8L payloads of encode_webp_frames -> a WebP file.  One frame: RIFF 'WEBP' { VP8L }.  Several: RIFF 'WEBP' { VP8X (flags 0x02 = animation,
     canvas W - 1 and H - 1 in 24 bits), ANIM (background 0, `loop` plays, 0 = for ever), per frame ANMF (offset 0 0, W - 1, H - 1, the duration in ms
-    in 24 bits, flags 0x02 = do not blend, do not dispose) wrapping one VP8L chunk }.  Chunks are padded to even length.  Returns the bytes
-    written."""
+    in 24 bits, flags 0x02 = do not blend, do not dispose) wrapping one VP8L chunk }.  Chunks are padded to even length.  lossy=True takes VP8
+    payloads of encode_vp8_frames instead and writes 'VP8 ' where VP8L stands above; nothing else changes.  Returns the bytes written."""
     blobs = [bytes(b) for b in blobs]
     W, H = int(W), int(H)
     if not blobs:
@@ -857,20 +914,24 @@ def write_webp(path, blobs, W, H, fps, loop=0):
     total = 12 + sum(8 + len(b) + (len(b) & 1) for b in blobs) + (0 if len(blobs) == 1 else 18 + 14 + 24 * len(blobs))
     if total > WEBP_MAX_BYTES:
         raise ValueError(f"write_webp: {path} would pass 4 GiB - 1 ({total} bytes); a RIFF size is 32 bits")
+    kind = b"VP8 " if lossy else b"VP8L"
     if len(blobs) == 1:
-        body = b"WEBP" + _chunk(b"VP8L", blobs[0])
+        body = b"WEBP" + _chunk(kind, blobs[0])
     else:
         size = _u24(W - 1) + _u24(H - 1)
         out = [b"WEBP", _chunk(b"VP8X", b"\x02\0\0\0" + size), _chunk(b"ANIM", struct.pack("<IH", 0, loop))]
-        out += [_chunk(b"ANMF", _u24(0) + _u24(0) + size + _u24(duration) + b"\x02" + _chunk(b"VP8L", b)) for b in blobs]
+        out += [_chunk(b"ANMF", _u24(0) + _u24(0) + size + _u24(duration) + b"\x02" + _chunk(kind, b)) for b in blobs]
         body = b"".join(out)
     assert len(body) + 8 == total
     return _write(path, b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
-def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90, gif_encoder="pil"):
+def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90, gif_encoder="pil", webp_quality=None):
+    """`quality` is the Motion-JPEG quality of .avi.  `webp_quality` = None writes .webp lossless; 0 .. 100 writes it lossy (VP8 key frames)."""
     if gif_encoder not in ("pil", "device"):
         raise ValueError(f"gif_encoder must be 'pil' or 'device', got {gif_encoder!r}")
+    if webp_quality is not None and not 0 <= int(webp_quality) <= 100:
+        raise ValueError(f"webp_quality must be None or 0 .. 100, got {webp_quality!r}")
     if rescale:
         if torch.as_tensor(videos).dtype == torch.uint8:
             raise ValueError("rescale=True maps [-1, 1] floats to [0, 1]; uint8 frames are already in their final range")
@@ -894,6 +955,8 @@ def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=
         write_avi(path, encode_jpeg_frames(frames, quality), frames.shape[2], frames.shape[1], fps)
     elif fmt in (".apng", ".png"):                                          # lossless; one frame gives an ordinary PNG
         write_apng(path, encode_png_frames(frames), frames.shape[2], frames.shape[1], fps)
+    elif fmt == ".webp" and webp_quality is not None:                       # lossy; one frame gives a plain VP8 file
+        write_webp(path, encode_vp8_frames(frames, int(webp_quality)), frames.shape[2], frames.shape[1], fps, lossy=True)
     elif fmt == ".webp":                                                    # lossless; one frame gives a plain VP8L file
         write_webp(path, encode_webp_frames(frames), frames.shape[2], frames.shape[1], fps)
     elif fmt == ".mp4":

@@ -62,6 +62,9 @@ def parse_args():
                         "PNG, pngs = a directory of 0000.png, 0001.png, ..., both filtered and deflated on the device; webp = lossless animated "
                         "WebP, predicted and prefix-coded on the device (mmgt_amd.video_out)")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
+    p.add_argument("--webp_quality", type=int, default=None,
+                   help="with --format webp: 0 .. 100 writes lossy animated WebP, every frame a VP8 key frame coded on the device "
+                        "(mmgt_amd.video_out.encode_vp8_frames); without it the .webp stays lossless")
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
                         "on the device: mmgt_amd.video_out.encode_gif_frames)")
@@ -259,7 +262,10 @@ def main():
         path = os.path.splitext(path)[0] + "_png"
         extra["files"] = len(write_png_sequence(path, encode_png_frames(v[0]), a.W, a.H))
     else:
-        save_videos_grid(v, path, n_rows=1, fps=a.fps or 25, gif_encoder=a.gif_encoder)
+        lossy = a.webp_quality if a.format == "webp" else None
+        save_videos_grid(v, path, n_rows=1, fps=a.fps or 25, gif_encoder=a.gif_encoder, webp_quality=lossy)
+        if lossy is not None:
+            extra["webp_quality"] = lossy
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
                       "dtype": a.dtype, "context_batch_size": a.context_batch_size, "keypoints_finite": bool(np.isfinite(kps).all()),
                       "mask_levels": [list(m.shape) for m in face], **timing, **extra}))

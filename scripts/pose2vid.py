@@ -58,6 +58,9 @@ def parse_args():
                         "directory of 0000.png, 0001.png, ..., both filtered and deflated on the device; webp = lossless animated WebP, predicted "
                         "and prefix-coded on the device (mmgt_amd.video_out); with --synthetic, apng / pngs / webp also write the clip that way")
     p.add_argument("--quality", type=int, default=90, help="JPEG quality (1 .. 100) of --format avi")
+    p.add_argument("--webp_quality", type=int, default=None,
+                   help="with --format webp: 0 .. 100 writes lossy animated WebP, every frame a VP8 key frame coded on the device "
+                        "(mmgt_amd.video_out.encode_vp8_frames); without it the .webp stays lossless")
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
                         "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
@@ -232,7 +235,10 @@ def run_files(a, dev, dtype):
         extra = {"files": len(write_png_sequence(path, encode_png_frames(frames_uint8(out.videos, 1)), a.W, a.H))}
         shape = list(torch.as_tensor(out.videos).shape)
     else:
-        save_videos_grid(out.videos, path, n_rows=1, fps=a.fps, gif_encoder=a.gif_encoder)
+        lossy = a.webp_quality if a.format == "webp" else None
+        save_videos_grid(out.videos, path, n_rows=1, fps=a.fps, gif_encoder=a.gif_encoder, webp_quality=lossy)
+        if lossy is not None:
+            extra = {"webp_quality": lossy}
         shape = list(torch.as_tensor(out.videos).shape)
     print(json.dumps({"video": shape, "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype,
@@ -321,8 +327,10 @@ def main():
     if a.format == "webp" and not a.no_decode:
         from mmgt_amd.video_out import save_videos_grid
         extra["webp"] = os.path.splitext(path)[0] + ".webp"
-        save_videos_grid(v, extra["webp"], n_rows=1, fps=a.fps)
+        save_videos_grid(v, extra["webp"], n_rows=1, fps=a.fps, webp_quality=a.webp_quality)
         extra["webp_bytes"] = os.path.getsize(extra["webp"])
+        if a.webp_quality is not None:
+            extra["webp_quality"] = a.webp_quality
     if a.format == "pngs" and not a.no_decode:
         from mmgt_amd.video_out import encode_png_frames, frames_uint8, write_png_sequence
         extra["pngs"] = os.path.splitext(path)[0] + "_png"
