@@ -774,39 +774,47 @@ def gemm_bf16_f32(a, w, out=None):
     return out
 
 
-def qk_split3(qk, bias_q, bias_k):
+def qk_split3(qk, bias_q, bias_k, out=None):
     """qk fp32 (rows, 4C) = [t Wq_hi^T | t Wq_lo^T | t Wk_hi^T | t Wk_lo^T] -> (Qp, Kp) bf16 (rows, 3C): [q_hi|q_hi|q_lo], [k_hi|k_lo|k_hi]
-    with q = qk0 + qk1 + bias_q, k = qk2 + qk3 + bias_k (so that Qp . Kp = q . k to ~17 bits on the bf16 MFMA path)."""
-    _dev(qk, bias_q, bias_k)
+    with q = qk0 + qk1 + bias_q, k = qk2 + qk3 + bias_k (so that Qp . Kp = q . k to ~17 bits on the bf16 MFMA path).  out = (Qp, Kp): write
+    into these contiguous bf16 (rows, 3C) tensors."""
+    _dev(qk, bias_q, bias_k, *(out or ()))
     assert qk.dim() == 2 and qk.is_contiguous() and qk.dtype == torch.float32 and qk.shape[1] % 16 == 0
     rows, C = qk.shape[0], qk.shape[1] // 4
     assert bias_q.shape == (C,) and bias_k.shape == (C,) and bias_q.dtype == torch.float32 and bias_k.dtype == torch.float32
-    Qp = torch.empty((rows, 3 * C), device=qk.device, dtype=torch.bfloat16)
-    Kp = torch.empty((rows, 3 * C), device=qk.device, dtype=torch.bfloat16)
+    if out is None:
+        out = (torch.empty((rows, 3 * C), device=qk.device, dtype=torch.bfloat16), torch.empty((rows, 3 * C), device=qk.device, dtype=torch.bfloat16))
+    Qp, Kp = out
+    for t in out:
+        assert t.shape == (rows, 3 * C) and t.dtype == torch.bfloat16 and t.is_contiguous()
     _check(lib().mmgt_qk_split3(_ptr(qk), _ptr(bias_q), _ptr(bias_k), _ptr(Qp), _ptr(Kp), rows, C, _stream()), "mmgt_qk_split3")
     return Qp, Kp
 
 
 # ------------------------------------------------------------------------------------------------------------ plumbing
 
-def ncfhw_to_nhwc(x, cpad, dtype, scale=1.0):
+def ncfhw_to_nhwc(x, cpad, dtype, scale=1.0, out=None):
     """(B, C, F, H, W) fp32 -> (B*F, H, W, cpad) channels-last `dtype` (times `scale`), zero padded channels."""
-    _dev(x)
+    _dev(x, out)
     assert x.dim() == 5 and x.dtype == torch.float32 and x.is_contiguous()
     B, C, F, H, W = x.shape
-    out = torch.empty((B * F, H, W, cpad), device=x.device, dtype=dtype)
+    if out is None:
+        out = torch.empty((B * F, H, W, cpad), device=x.device, dtype=dtype)
+    assert out.shape == (B * F, H, W, cpad) and out.dtype == dtype and out.is_contiguous()
     _check(lib().mmgt_ncfhw_to_nhwc(_ptr(x), _ptr(out), B, C, F, H, W, cpad, scale, dtype_code(dtype), _stream()),
            "mmgt_ncfhw_to_nhwc")
     return out
 
 
-def nhwc_to_ncfhw(x, B, C, scale=1.0, shift=0.0, clamp01=False):
+def nhwc_to_ncfhw(x, B, C, scale=1.0, shift=0.0, clamp01=False, out=None):
     """(B*F, H, W, cpad) -> (B, C, F, H, W) fp32 (first C channels), out = clamp(x * scale + shift)."""
-    _dev(x)
+    _dev(x, out)
     assert x.dim() == 4 and x.is_contiguous()
     BF, H, W, cpad = x.shape
     F = BF // B
-    out = torch.empty((B, C, F, H, W), device=x.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((B, C, F, H, W), device=x.device, dtype=torch.float32)
+    assert out.shape == (B, C, F, H, W) and out.dtype == torch.float32 and out.is_contiguous()
     _check(lib().mmgt_nhwc_to_ncfhw(_ptr(x), _ptr(out), B, C, F, H, W, cpad, scale, shift, int(clamp01),
                                     dtype_code(x.dtype), _stream()),
            "mmgt_nhwc_to_ncfhw")
@@ -834,40 +842,55 @@ def conv1x1_cat(x0, x1, w, bias=None, residual=None, out=None):
     return out
 
 
-def conv_taps_gather(y, bias, NB, H, W):
+def conv_taps_gather(y, bias, NB, H, W, out=None):
     """y (NB * H * W, ldY >= 36) bf16 = the per-pixel products of a 4-channel 3 x 3 conv (column 4 tap + o: packing.pack_conv_taps) -> (NB, H, W, 8) bf16:
     channels 0 .. 3 = bias + the sum over the taps of the neighbour pixels' products, 4 .. 7 zero."""
-    _dev(y, bias)
+    _dev(y, bias, out)
     assert y.dim() == 2 and y.shape[0] == NB * H * W and y.shape[1] >= 36 and y.stride(1) == 1 and y.dtype == torch.bfloat16
-    out = torch.empty((NB, H, W, 8), device=y.device, dtype=y.dtype)
+    if out is None:
+        out = torch.empty((NB, H, W, 8), device=y.device, dtype=y.dtype)
+    assert out.shape == (NB, H, W, 8) and out.dtype == y.dtype and out.is_contiguous()
     _check(lib().mmgt_conv_taps_gather(_ptr(y), y.stride(0), _ptr(_f32(bias, "bias")), _ptr(out), NB, H, W, dtype_code(y.dtype), _stream()),
            "mmgt_conv_taps_gather")
     return out
 
 
-def timestep_features(timesteps, dim, dtype):
-    _dev(timesteps)
-    assert timesteps.dtype == torch.float32 and timesteps.dim() == 1
-    out = torch.empty((timesteps.shape[0], dim), device=timesteps.device, dtype=dtype)
+def timestep_features(timesteps, dim, dtype, out=None):
+    _dev(timesteps, out)
+    assert timesteps.dtype == torch.float32 and timesteps.dim() == 1 and timesteps.is_contiguous()
+    if out is None:
+        out = torch.empty((timesteps.shape[0], dim), device=timesteps.device, dtype=dtype)
+    assert out.shape == (timesteps.shape[0], dim) and out.dtype == dtype and out.is_contiguous()
     _check(lib().mmgt_timestep_features(_ptr(timesteps), _ptr(out), timesteps.shape[0], dim, dtype_code(dtype),
                                         _stream()), "mmgt_timestep_features")
     return out
 
 
-def silu(x):
-    _dev(x)
+def silu(x, out=None):
+    _dev(x, out)
     assert x.is_contiguous()
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous()
     _check(lib().mmgt_silu(_ptr(x), _ptr(out), x.numel(), dtype_code(x.dtype), _stream()), "mmgt_silu")
     return out
 
 
-def cfg_ddim_step(pred_sum, counter, latents, guidance, sa_t, sb_t, sa_p, sb_p):
-    """latents (1, C, F, H, W) fp32; pred_sum (2, C, F, H, W) fp32; counter (F,) fp32 -> new latents."""
-    _dev(pred_sum, counter, latents)
+def cfg_ddim_step(pred_sum, counter, latents, guidance, sa_t, sb_t, sa_p, sb_p, out=None):
+    """latents (1, C, F, H, W) fp32; pred_sum (2, C, F, H, W) fp32; counter (F,) fp32 -> new latents.  The kernel takes latents.numel() as
+    the stride between the two CFG rows of pred_sum and indexes counter by frame: any other shape is refused before the launch."""
+    _dev(pred_sum, counter, latents, out)
     assert latents.dtype == torch.float32 and latents.is_contiguous() and pred_sum.is_contiguous()
+    if latents.dim() != 5 or latents.shape[0] != 1:
+        raise RuntimeError(f"cfg_ddim_step: latents must be (1, C, F, H, W), got {tuple(latents.shape)}")
+    if pred_sum.dtype != torch.float32 or tuple(pred_sum.shape) != (2,) + tuple(latents.shape[1:]):
+        raise RuntimeError(f"cfg_ddim_step: pred_sum must be float32 {(2,) + tuple(latents.shape[1:])}, got {pred_sum.dtype} {tuple(pred_sum.shape)}")
     _, C, F, H, W = latents.shape
-    out = torch.empty_like(latents)
+    if counter.numel() != F:
+        raise RuntimeError(f"cfg_ddim_step: counter has {counter.numel()} entries for {F} frames")
+    if out is None:
+        out = torch.empty_like(latents)
+    assert out.shape == latents.shape and out.dtype == torch.float32 and out.is_contiguous()
     _check(lib().mmgt_cfg_ddim_step(_ptr(pred_sum), _ptr(_f32(counter, "counter")), _ptr(latents), _ptr(out),
                                     latents.numel(), F, H * W, guidance, sa_t, sb_t, sa_p, sb_p, _stream()),
            "mmgt_cfg_ddim_step")
@@ -883,6 +906,12 @@ def accumulate_window(pred, pred_sum, counter, idx, C, rows=2, row0=0, bump_coun
     F = pred_sum.shape[2]
     hw = pred.shape[1] * pred.shape[2]
     assert pred.shape[0] == rows * Fw and pred_sum.shape[0] == 2 and pred_sum.shape[3] * pred_sum.shape[4] == hw
+    if pred_sum.dtype != torch.float32 or counter.dtype != torch.float32:
+        raise RuntimeError(f"accumulate_window: pred_sum and counter must be float32, got {pred_sum.dtype} and {counter.dtype}")
+    if pred_sum.shape[1] != C:
+        raise RuntimeError(f"accumulate_window: pred_sum has {pred_sum.shape[1]} channels, C = {C}")
+    if counter.numel() != F or not counter.is_contiguous():
+        raise RuntimeError(f"accumulate_window: counter has {counter.numel()} entries for {F} frames")
     _check(lib().mmgt_accumulate_window_rows(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), Fw, F, C, pred.shape[3],
                                              hw, rows, row0, int(bump_counter), dtype_code(pred.dtype), _stream()),
            "mmgt_accumulate_window_rows")
