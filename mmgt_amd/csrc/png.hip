@@ -8,28 +8,21 @@
 //                        sums[row] = { sum d[i], sum (L - i) d[i] } over the L = 1 + 3 W bytes, in 64 bits (the host reduces and combines them).
 //  * mmgt_png_histogram  any bytes, n rows of frame_bytes cut into strips of strip_bytes (the last may be shorter) -> u32[286] per strip: how often
 //  * mmgt_png_deflate    each literal/length symbol occurs in the strip's tokens, and those tokens coded with the strip's own table behind the
-//                        strip's header bits.  Tokens: distance-1 matches only, never reaching before the strip's first byte.  At position p >= 1 let
-//                        r = bytes from p on that equal byte p - 1, at most 258: r >= 3 is a match of length r, else byte p is a literal; position 0
-//                        is a literal; symbol 256 closes the block.  That greedy parse has a closed form: in a maximal run of equal bytes the first is
-//                        a literal and the k bytes after it fall into blocks of 258 (the last one shorter), a block of 3 or more being one match and
-//                        one of 1 or 2 literals.  A token is credited to the position where it ENDS, so that a position needs only the start of
-//                        its run (a max-scan over the positions before it) and the two bytes after it: with j = p - run start - 1 and m = j mod 258,
-//                        m = 257 ends a match of 258; a run ending at p ends a match of m + 1 if that is 3 or more, else p is a literal; and m = 0
-//                        in a run that goes on for one byte only is the first of two literals.  One workgroup per strip walks it 256 positions at a
-//                        time: token bits by table, workgroup prefix sum, atomicOr into LDS words, whole words stored to the strip's slot and the
-//                        partly filled last word carried on; so every word of a slot is written once, with plain stores.
+//                        strip's header bits.  Tokens: distance-1 matches only, never reaching before the strip's first byte, at most 258 long, by
+//                        the closed form of csrc/strip_coder.h; symbol 256 closes the block.  One workgroup per strip; the walk (scans, LDS window,
+//                        carried word, every word of a slot written once with plain stores) is strip_coder.h's sc_walk_strip, shared with
+//                        csrc/webp.hip.  What is PNG's own is below: the token's symbol and extra bits, the strip's table and its header in front.
 //  * mmgt_png_pack       joins a frame's strips at the bit offsets the host worked out and writes the frames' deflate bytes back to back.
 #include "common.h"
 #include "mmgt_hip.h"
+#include "strip_coder.h"
 
 namespace {
 
 constexpr int kSyms = 286;
-constexpr int kThreads = 256;
+constexpr int kThreads = kScThreads;
 constexpr int kMaxSide = 16384;
 constexpr int kHeaderWords = MMGT_PNG_HEADER_BYTES / 4;            // 17 + 19 * 3 + 316 * 14 bits at most = 4498 bits = 141 words
-constexpr int kTokenBits = 21;                                     // a length code of 15 bits, 5 extra bits, the distance code's single bit
-constexpr int kChunkWords = (kThreads * kTokenBits + 31) / 32 + 2; // the carried partial word in front, one word for a token straddling the end
 
 // ---- filter ------------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int paeth(int a, int b, int c) {
@@ -96,36 +89,6 @@ __global__ __launch_bounds__(kThreads) void png_filter_kernel(const unsigned cha
 }
 
 // ---- tokens ------------------------------------------------------------------------------------------------------------------------------------
-// Inclusive scans over the workgroup's 256 threads (4 waves): within a wave by shuffles, then the totals of the waves before through LDS.  Both end
-// with every thread past the barrier that guards part_s, so they can be called back to back.
-__device__ __forceinline__ int block_scan_max(int v, int* part_s) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v = max(v, o);
-  }
-  if (lane == 63) part_s[wave] = v;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) v = max(v, part_s[w]);
-  __syncthreads();
-  return v;
-}
-__device__ __forceinline__ int block_scan_add(int v, int* part_s, int* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  if (lane == 63) part_s[wave] = v;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) v += part_s[w];
-  *total = part_s[0] + part_s[1] + part_s[2] + part_s[3];
-  __syncthreads();
-  return v;
-}
-
 // length 3 .. 258 -> literal/length symbol, extra bits and their value (RFC 1951 3.2.5)
 __device__ __forceinline__ void length_symbol(int len, int* sym, int* ebits, int* eval) {
   const int x = len - 3;
@@ -139,19 +102,36 @@ __device__ __forceinline__ void length_symbol(int len, int* sym, int* ebits, int
   }
 }
 
-// The token that ends at position p of a strip of len bytes: -1 none, 0 .. 255 the literal, 3 .. 258 | 0x1000 a match.  p == len is the end-of-block
-// symbol 256.  run_start = the last position q <= p that is 0 or whose byte differs from byte q - 1.
+// The token that ends at position p of a strip of len bytes: -1 none, 0 .. 255 the literal, 3 .. 258 | 0x1000 a match (strip_coder.h's closed form
+// at 258).  p == len is the end-of-block symbol 256.
 __device__ __forceinline__ int token_at(const unsigned char* __restrict__ src, int p, int len, int run_start) {
   if (p == len) return 256;
-  const int d = src[p];
-  if (p == run_start) return d;
-  const int m = (p - run_start - 1) % 258;
-  if (m == 257) return 258 | 0x1000;
-  const bool c1 = p + 1 < len && src[p + 1] == d;
-  if (!c1) return m >= 2 ? ((m + 1) | 0x1000) : d;
-  const bool c2 = p + 2 < len && src[p + 2] == d;
-  return (m == 0 && !c2) ? d : -1;
+  const int d = src[p];                                            // read before the token is known: one round trip less for a literal
+  const int tok = sc_token_at<258>(ScSameAsBefore<unsigned char>{src}, p, len, run_start);
+  return tok == SC_NONE ? -1 : tok == SC_LITERAL ? d : tok | 0x1000;
 }
+
+// strip_coder.h's codec of deflate: a token is a literal/length symbol of the strip's table; a match adds its extra bits and the distance code 0.
+struct PngCodec {
+  using Elem = unsigned char;
+  static constexpr int kTokenBits = 21;                            // a length code of 15 bits, 5 extra bits, the distance code's single bit
+  static constexpr int kTail = 1;                                  // position len is the end-of-block symbol
+  static __device__ __forceinline__ int token(const Elem* src, int p, int len, int run_start) { return token_at(src, p, len, run_start); }
+  static __device__ __forceinline__ void count(unsigned* tab_s, int tok, const Elem*, int) {
+    int sym = tok, ebits = 0, eval = 0;
+    if (tok >= 0x1000) length_symbol(tok & 0xfff, &sym, &ebits, &eval);
+    atomicAdd(&tab_s[sym], 1u);
+  }
+  static __device__ __forceinline__ ScFields fields(const unsigned* tab_s, int tok, const Elem*, int) {
+    int sym = tok, ebits = 0, eval = 0;
+    if (tok >= 0x1000) length_symbol(tok & 0xfff, &sym, &ebits, &eval);
+    const unsigned c = tab_s[sym];
+    ScFields f;
+    f.v0 = (unsigned long long)(c & 0xffffu) | (unsigned long long)eval << (c >> 16);   // a match: extra bits, then the distance code 0 (one bit)
+    f.n0 = (int)(c >> 16) + ebits + (tok >= 0x1000 ? 1 : 0);
+    return f;
+  }
+};
 
 template <bool kEmit>
 __global__ __launch_bounds__(kThreads) void png_strip_kernel(const unsigned char* __restrict__ data, long long frame_bytes, long long strip_bytes, int strips,
@@ -160,89 +140,19 @@ __global__ __launch_bounds__(kThreads) void png_strip_kernel(const unsigned char
                                                              unsigned* __restrict__ slots, const long long* __restrict__ slot_off, long long slots_words,
                                                              long long* __restrict__ bits) {
   __shared__ unsigned tab_s[kSyms];                                // the histogram, or the strip's code table
-  __shared__ unsigned w_s[kChunkWords];
-  __shared__ int part_s[4];
-  __shared__ int carry_s;
   const int t = threadIdx.x;
   const int strip = blockIdx.x % strips;
   const size_t frame = blockIdx.x / strips;
   const long long first = (long long)strip * strip_bytes;
   const int len = (int)min(strip_bytes, frame_bytes - first);      // 1 .. 2^30
   const unsigned char* src = data + frame * (size_t)frame_bytes + (size_t)first;
-
-  // the slot: words [w_lo, w_lo + w_cap) of slots, clamped to the buffer whatever slot_off holds
-  long long w_lo = 0, w_cap = 0;
-  long long bitpos = 0;
-  unsigned carry = 0u;                                             // the bits of the word that bitpos lies in
-  if (kEmit) {
-    w_lo = slot_off[blockIdx.x];
-    w_cap = slot_off[blockIdx.x + 1] - w_lo;
-    if (w_lo < 0 || w_lo > slots_words) w_lo = slots_words;
-    w_cap = max(0ll, min(w_cap, slots_words - w_lo));
-    for (int i = t; i < kSyms; i += kThreads) tab_s[i] = codes[(size_t)blockIdx.x * kSyms + i];
+  for (int i = t; i < kSyms; i += kThreads) tab_s[i] = kEmit ? codes[(size_t)blockIdx.x * kSyms + i] : 0u;
+  if (kEmit) {                                                     // the strip's own table, and its block header in front of the tokens
     const int hb = max(0, min(header_bits[blockIdx.x], 32 * kHeaderWords));
-    const unsigned* hw = header + (size_t)blockIdx.x * kHeaderWords;
-    for (int i = t; i < hb / 32; i += kThreads)
-      if (i < w_cap) slots[w_lo + i] = hw[i];
-    if (hb & 31) carry = hw[hb / 32] & ((1u << (hb & 31)) - 1u);
-    bitpos = hb;
+    sc_walk_strip<true, PngCodec>(src, len, tab_s, header + (size_t)blockIdx.x * kHeaderWords, hb, slots, slot_off + blockIdx.x, slots_words,
+                                  bits + blockIdx.x);
   } else {
-    for (int i = t; i < kSyms; i += kThreads) tab_s[i] = 0u;
-  }
-  if (t == 0) carry_s = -1;
-  __syncthreads();
-
-  for (int base = 0; base <= len; base += kThreads) {             // position len is the end-of-block symbol
-    const int p = base + t;
-    const bool valid = p <= len;
-    const bool boundary = p < len && (p == 0 || src[p] != src[p - 1]);
-    if (kEmit) {
-      for (int i = t; i < kChunkWords; i += kThreads) w_s[i] = i == 0 ? carry : 0u;
-    }
-    const int run_start = max(block_scan_max(boundary ? p : -1, part_s), carry_s);
-    const int tok = valid ? token_at(src, p, len, run_start) : -1;
-    int sym = tok, ebits = 0, eval = 0;
-    if (tok >= 0x1000) length_symbol(tok & 0xfff, &sym, &ebits, &eval);
-    if (!kEmit) {
-      if (tok >= 0) atomicAdd(&tab_s[sym], 1u);
-      __syncthreads();                                             // carry_s is read above by every thread before it is rewritten
-    } else {
-      unsigned long long v = 0;
-      int nb = 0;
-      if (tok >= 0) {
-        const unsigned c = tab_s[sym];
-        const int cl = (int)(c >> 16);
-        v = (unsigned long long)(c & 0xffffu) | (unsigned long long)eval << cl;       // a match: extra bits, then the distance code 0 (one bit)
-        nb = cl + ebits + (tok >= 0x1000 ? 1 : 0);
-      }
-      int total;
-      const int end = block_scan_add(nb, part_s, &total);
-      const int off0 = (int)(bitpos & 31);
-      if (nb > 0) {
-        const int at = off0 + end - nb;                            // < 32 + 256 * 21
-        const unsigned long long sh = v << (at & 31);              // nb <= 21 and at & 31 <= 31: fits
-        atomicOr(&w_s[at >> 5], (unsigned)sh);
-        if ((unsigned)(sh >> 32)) atomicOr(&w_s[(at >> 5) + 1], (unsigned)(sh >> 32));
-      }
-      __syncthreads();
-      const int full = (off0 + total) >> 5;
-      const long long w0 = bitpos >> 5;
-      for (int i = t; i < full; i += kThreads)
-        if (w0 + i < w_cap) slots[w_lo + w0 + i] = w_s[i];
-      carry = w_s[full];
-      bitpos += total;
-      __syncthreads();                                             // w_s is cleared by the next round
-    }
-    if (t == kThreads - 1) carry_s = run_start;
-    __syncthreads();
-  }
-
-  if (kEmit) {
-    if (t == 0) {
-      if ((bitpos & 31) && (bitpos >> 5) < w_cap) slots[w_lo + (bitpos >> 5)] = carry;
-      bits[blockIdx.x] = bitpos;
-    }
-  } else {
+    sc_walk_strip<false, PngCodec>(src, len, tab_s, nullptr, 0, nullptr, nullptr, 0ll, nullptr);
     for (int i = t; i < kSyms; i += kThreads) hist[(size_t)blockIdx.x * kSyms + i] = tab_s[i];
   }
 }
@@ -285,13 +195,8 @@ __global__ __launch_bounds__(256) void png_pack_kernel(const unsigned* __restric
   }
 }
 
-const char* kBadStrips = "%s: n = %d rows of %lld bytes in strips of %lld are outside the range (n >= 1, 1 <= strip_bytes, 1 <= frame_bytes <= 2^30, "
-                         "n * strips < 2^31)";
-bool strips_ok(int n, long long frame_bytes, long long strip_bytes) {
-  if (n < 1 || frame_bytes < 1 || frame_bytes > (1ll << 30) || strip_bytes < 1) return false;
-  const long long strips = (frame_bytes + strip_bytes - 1) / strip_bytes;
-  return n * strips <= 0x7fffffffll;
-}
+const char* kBadStrips = SC_BAD_STRIPS("bytes", "bytes", "2^30");
+constexpr long long kMaxFrameBytes = 1ll << 30;
 
 }  // namespace
 
@@ -307,7 +212,7 @@ extern "C" int mmgt_png_filter(const unsigned char* frames, unsigned char* filt,
 
 extern "C" int mmgt_png_histogram(const unsigned char* data, unsigned* hist, int n, long long frame_bytes, long long strip_bytes, void* stream) {
   MMGT_CHECK(data && hist, "png_histogram: null pointer");
-  MMGT_CHECK(strips_ok(n, frame_bytes, strip_bytes), kBadStrips, "png_histogram", n, frame_bytes, strip_bytes);
+  MMGT_CHECK(sc_strips_ok(n, frame_bytes, strip_bytes, kMaxFrameBytes), kBadStrips, "png_histogram", n, frame_bytes, strip_bytes);
   const int strips = (int)((frame_bytes + strip_bytes - 1) / strip_bytes);
   hipLaunchKernelGGL(png_strip_kernel<false>, dim3((unsigned)(n * strips)), dim3(kThreads), 0, (hipStream_t)stream, data, frame_bytes, strip_bytes,
                      strips, hist, nullptr, nullptr, nullptr, nullptr, nullptr, 0ll, nullptr);
@@ -319,7 +224,7 @@ extern "C" int mmgt_png_deflate(const unsigned char* data, const unsigned* codes
                                 const long long* slot_off, long long slots_words, long long* bits, int n, long long frame_bytes, long long strip_bytes,
                                 void* stream) {
   MMGT_CHECK(data && codes && header && header_bits && slots && slot_off && bits, "png_deflate: null pointer");
-  MMGT_CHECK(strips_ok(n, frame_bytes, strip_bytes), kBadStrips, "png_deflate", n, frame_bytes, strip_bytes);
+  MMGT_CHECK(sc_strips_ok(n, frame_bytes, strip_bytes, kMaxFrameBytes), kBadStrips, "png_deflate", n, frame_bytes, strip_bytes);
   MMGT_CHECK(slots_words >= 1, "png_deflate: slots_words = %lld", slots_words);
   const int strips = (int)((frame_bytes + strip_bytes - 1) / strip_bytes);
   hipLaunchKernelGGL(png_strip_kernel<true>, dim3((unsigned)(n * strips)), dim3(kThreads), 0, (hipStream_t)stream, data, frame_bytes, strip_bytes,

@@ -5,6 +5,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "strip_coder.h"
+
 #if defined(__HIPCC__)
 #define WP_HD __host__ __device__ inline
 #else
@@ -17,8 +19,8 @@ enum {
   WP_MAX_LENGTH = 4096,        // the longest match
   WP_GREEN_SYMS = 280,         // 256 literals + 24 length prefixes (no colour cache)
   WP_HIST_WORDS = 280 + 256 + 256 + 1,  // green + length, red, blue, then the number of matches
-  WP_LITERAL = 0,              // wp_token_at: pixel p is a literal
-  WP_NONE = -1                 // wp_token_at: no token ends at p
+  WP_LITERAL = SC_LITERAL,     // wp_token_at: pixel p is a literal
+  WP_NONE = SC_NONE            // wp_token_at: no token ends at p
 };
 #define WP_BLACK 0xff000000u
 
@@ -108,19 +110,9 @@ WP_HD unsigned wp_cost(uint32_t res) {
 }
 
 // The token that ends at position p of a strip of len pixels: WP_NONE, WP_LITERAL (pixel p itself) or the length 3 .. 4096 of a match from the left
-// pixel.  run_start = the last position q <= p that is 0 or whose pixel differs from pixel q - 1.  In a maximal run of equal pixels the first is a
-// literal and the pixels after it fall into blocks of 4096 (the last one shorter), a block of 3 or more being one match and one of 1 or 2 literals:
-// with m = (p - run_start - 1) mod 4096, m = 4095 ends a match of 4096; a run ending at p ends a match of m + 1 if that is 3 or more, else p is a
-// literal; and m = 0 in a run that goes on for one pixel only is the first of two literals.
+// pixel: strip_coder.h's closed form at 4096.  run_start = the last position q <= p that is 0 or whose pixel differs from pixel q - 1.
 WP_HD int wp_token_at(const uint32_t* src, int p, int len, int run_start) {
-  if (p == run_start) return WP_LITERAL;
-  const uint32_t d = src[p];
-  const int m = (p - run_start - 1) % WP_MAX_LENGTH;
-  if (m == WP_MAX_LENGTH - 1) return WP_MAX_LENGTH;
-  const bool c1 = p + 1 < len && src[p + 1] == d;
-  if (!c1) return m >= 2 ? m + 1 : WP_LITERAL;
-  const bool c2 = p + 2 < len && src[p + 2] == d;
-  return (m == 0 && !c2) ? WP_LITERAL : WP_NONE;
+  return sc_token_at<WP_MAX_LENGTH>(ScSameAsBefore<uint32_t>{src}, p, len, run_start);
 }
 
 // A length (or distance) value 1 .. 4096 -> its prefix symbol, the number of extra bits and their value.

@@ -1212,7 +1212,7 @@ def jpegdec_color(planes, H, W, ncomp, hs, vs, out=None):
 GIF_BINS = 32768
 
 
-def _gif_frames(frames, what):
+def _rgb_frames(frames, what):
     _dev(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or not frames.is_contiguous():
         raise RuntimeError(f"{what}: frames must be contiguous uint8 (n, H, W, 3)")
@@ -1222,7 +1222,7 @@ def _gif_frames(frames, what):
 def gif_histogram(frames):
     """(n, H, W, 3) uint8 RGB -> (32768,) pixels per 5-bit-per-channel bin (r >> 3) << 10 | (g >> 3) << 5 | (b >> 3) of the whole clip, on the
     device.  The counts are uint32 held in an int32 tensor: read them with .cpu().numpy().view(numpy.uint32)."""
-    n, H, W = _gif_frames(frames, "gif_histogram")
+    n, H, W = _rgb_frames(frames, "gif_histogram")
     hist = torch.zeros((GIF_BINS,), device=frames.device, dtype=torch.int32)
     _check(lib().mmgt_gif_histogram(_ptr(frames), _ptr(hist), n, H, W, _stream()), "mmgt_gif_histogram")
     return hist
@@ -1230,7 +1230,7 @@ def gif_histogram(frames):
 
 def gif_index(frames, lut):
     """idx (n, H, W) uint8 = lut[bin(pixel)]; lut (32768,) uint8 on the device."""
-    n, H, W = _gif_frames(frames, "gif_index")
+    n, H, W = _rgb_frames(frames, "gif_index")
     _dev(lut)
     if lut.dtype != torch.uint8 or tuple(lut.shape) != (GIF_BINS,) or not lut.is_contiguous():
         raise RuntimeError("gif_index: lut must be contiguous uint8 (32768,)")
@@ -1296,7 +1296,7 @@ PNG_HEADER_BYTES = 576              # MMGT_PNG_HEADER_BYTES: room for the longes
 def png_filter(frames, out=None):
     """(n, H, W, 3) uint8 RGB -> (filt (n, H, 1 + 3 W) uint8, sums (n, H, 2) int64): every scanline's filter type byte and filtered bytes, and the
     two sums of which the host makes the row's Adler-32 (see mmgt_png_filter).  `out` = (filt, sums) to write into."""
-    n, H, W = _gif_frames(frames, "png_filter")
+    n, H, W = _rgb_frames(frames, "png_filter")
     if out is None:
         out = (torch.empty((n, H, 1 + 3 * W), device=frames.device, dtype=torch.uint8),
                torch.empty((n, H, 2), device=frames.device, dtype=torch.int64))
@@ -1326,13 +1326,43 @@ def png_histogram(data, strip_bytes, out=None):
     return out
 
 
+def _slot_offsets(want_bits):
+    """Bit counts, one per slot -> word offsets (slots + 1,) int64 of slots that hold them, each a whole number of 32-bit words."""
+    import numpy as np
+    w = np.asarray(want_bits, np.int64).reshape(-1)
+    return np.concatenate([[0], np.cumsum((w + 31) // 32)]).astype(np.int64)
+
+
+def _pack_slots(slots, want_bits, out):
+    """Slots laid out by _slot_offsets(want_bits), want_bits (n, k) -> (packed (bytes,) uint8, out_off (n + 1,) host int64): frame f's k slots joined
+    bit by bit and padded with zero bits to a byte are packed[out_off[f]:out_off[f + 1]] (mmgt_png_pack)."""
+    import numpy as np
+    _dev(slots)
+    w = np.asarray(want_bits, np.int64)
+    n, k = w.shape
+    off = _slot_offsets(w)
+    bit_off = np.concatenate([np.zeros((n, 1), np.int64), np.cumsum(w, axis=1)], axis=1)
+    out_off = np.concatenate([[0], np.cumsum((bit_off[:, -1] + 7) // 8)]).astype(np.int64)
+    if out is None:
+        out = torch.empty((int(out_off[-1]),), device=slots.device, dtype=torch.uint8)
+    assert slots.dim() == 1 and slots.numel() >= int(off[-1]) and slots.dtype == torch.int32 and slots.is_contiguous()
+    assert out.dim() == 1 and out.numel() >= int(out_off[-1]) and out.dtype == torch.uint8 and out.is_contiguous()
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(slots.device)
+    for f0 in range(0, n, 65535):                                  # the launch's grid holds a frame per y index
+        f1 = min(n, f0 + 65535)
+        d_off, d_bit, d_out = up(off[f0 * k:f1 * k + 1]), up(bit_off[f0:f1]), up(out_off[f0:f1 + 1])                                # alive until launched
+        _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, k,
+                                   _stream()), "mmgt_png_pack")
+    return out, out_off
+
+
 def png_slot_offsets(want_bits):
     """Exact bit counts (n, strips) -> word offsets (n * strips + 1,) int64 of slots that hold them, each a whole number of 32-bit words."""
     import numpy as np
-    w = np.asarray(want_bits, np.int64).reshape(-1)
+    w = np.asarray(want_bits, np.int64)
     if w.size == 0 or (w < 1).any():
         raise RuntimeError("png: every strip holds at least one bit")
-    return np.concatenate([[0], np.cumsum((w + 31) // 32)]).astype(np.int64)
+    return _slot_offsets(w)
 
 
 def png_deflate(data, strip_bytes, codes, headers, header_bits, want_bits, out=None):
@@ -1362,24 +1392,8 @@ def png_deflate(data, strip_bytes, codes, headers, header_bits, want_bits, out=N
 def png_pack(slots, want_bits, out=None):
     """The slots of png_deflate, laid out by the same want_bits (n, strips) -> (packed (bytes,) uint8, out_off (n + 1,) host int64): frame f's
     deflate stream, its strips joined bit by bit, is packed[out_off[f]:out_off[f + 1]].  `out` = packed to write into."""
-    import numpy as np
-    _dev(slots)
-    w = np.asarray(want_bits, np.int64)
-    n, strips = w.shape
-    off = png_slot_offsets(w)
-    bit_off = np.concatenate([np.zeros((n, 1), np.int64), np.cumsum(w, axis=1)], axis=1)
-    out_off = np.concatenate([[0], np.cumsum((bit_off[:, -1] + 7) // 8)]).astype(np.int64)
-    if out is None:
-        out = torch.empty((int(out_off[-1]),), device=slots.device, dtype=torch.uint8)
-    assert slots.dim() == 1 and slots.numel() >= int(off[-1]) and slots.dtype == torch.int32 and slots.is_contiguous()
-    assert out.dim() == 1 and out.numel() >= int(out_off[-1]) and out.dtype == torch.uint8 and out.is_contiguous()
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(slots.device)
-    for f0 in range(0, n, 65535):                                  # the launch's grid holds a frame per y index
-        f1 = min(n, f0 + 65535)
-        d_off, d_bit, d_out = up(off[f0 * strips:f1 * strips + 1]), up(bit_off[f0:f1]), up(out_off[f0:f1 + 1])                      # alive until launched
-        _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, strips,
-                                   _stream()), "mmgt_png_pack")
-    return out, out_off
+    png_slot_offsets(want_bits)                                    # PNG's rule for the counts
+    return _pack_slots(slots, want_bits, out)
 
 
 # ------------------------------------------------------------------------------------------------------------ WebP lossless (csrc/webp.hip)
@@ -1392,7 +1406,7 @@ WEBP_CODE_WORDS = 792               # a frame's code tables: green + length, red
 def webp_predict(frames, out=None):
     """(n, H, W, 3) uint8 RGB -> (modes (n, bh, bw) uint8, res (n, H, W) int32): every 16 x 16 block's predictor mode and the residuals as ARGB
     words (see mmgt_webp_predict).  `out` = (modes, res) to write into."""
-    n, H, W = _gif_frames(frames, "webp_predict")
+    n, H, W = _rgb_frames(frames, "webp_predict")
     B = 1 << WEBP_PREDICTOR_BITS
     bh, bw = -(-H // B), -(-W // B)
     if out is None:
@@ -1430,7 +1444,7 @@ def webp_slot_offsets(want_bits):
     w = np.asarray(want_bits, np.int64)
     if w.ndim != 2 or w.shape[1] < 2 or w.shape[0] < 1 or (w < 0).any() or (w[:, 0] < 1).any():
         raise RuntimeError("webp: bit counts are (n, 1 + strips), none negative, every header at least one bit")
-    return np.concatenate([[0], np.cumsum((w.reshape(-1) + 31) // 32)]).astype(np.int64)
+    return _slot_offsets(w)
 
 
 def webp_code(data, strip_px, codes, headers, want_bits, out=None):
@@ -1467,24 +1481,8 @@ def webp_pack(slots, want_bits, out=None):
     """The slots of webp_code, laid out by the same want_bits (n, 1 + strips) -> (packed (bytes,) uint8, out_off (n + 1,) host int64): frame f's VP8L
     payload, its header and strips joined bit by bit and padded with zero bits to a byte, is packed[out_off[f]:out_off[f + 1]].  The join is
     mmgt_png_pack's, with the header as one more slot.  `out` = packed to write into."""
-    import numpy as np
-    _dev(slots)
-    w = np.asarray(want_bits, np.int64)
-    off = webp_slot_offsets(w)
-    n, k = w.shape
-    bit_off = np.concatenate([np.zeros((n, 1), np.int64), np.cumsum(w, axis=1)], axis=1)
-    out_off = np.concatenate([[0], np.cumsum((bit_off[:, -1] + 7) // 8)]).astype(np.int64)
-    if out is None:
-        out = torch.empty((int(out_off[-1]),), device=slots.device, dtype=torch.uint8)
-    assert slots.dim() == 1 and slots.numel() >= int(off[-1]) and slots.dtype == torch.int32 and slots.is_contiguous()
-    assert out.dim() == 1 and out.numel() >= int(out_off[-1]) and out.dtype == torch.uint8 and out.is_contiguous()
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(slots.device)
-    for f0 in range(0, n, 65535):                                  # the launch's grid holds a frame per y index
-        f1 = min(n, f0 + 65535)
-        d_off, d_bit, d_out = up(off[f0 * k:f1 * k + 1]), up(bit_off[f0:f1]), up(out_off[f0:f1 + 1])                                # alive until launched
-        _check(lib().mmgt_png_pack(_ptr(slots), _ptr(d_off), slots.numel(), _ptr(d_bit), _ptr(out), _ptr(d_out), out.numel(), f1 - f0, k,
-                                   _stream()), "mmgt_png_pack")
-    return out, out_off
+    webp_slot_offsets(want_bits)                                   # WebP's rule for the counts
+    return _pack_slots(slots, want_bits, out)
 
 
 # ------------------------------------------------------------------------------------------------------------ WebP lossy (csrc/vp8.hip)
@@ -1522,7 +1520,7 @@ def _vp8_check_planes(planes, n, H, W, what):
 
 def vp8_convert(frames, out=None):
     """(n, H, W, 3) uint8 RGB -> (Y, U, V) of the frames padded to whole macroblocks (see mmgt_vp8_convert).  `out` = the planes to write into."""
-    n, H, W = _gif_frames(frames, "vp8_convert")
+    n, H, W = _rgb_frames(frames, "vp8_convert")
     if out is None:
         out = _vp8_planes(n, H, W, frames.device)
     if min(n, H, W) >= 1 and max(H, W) <= VP8_MAX_SIDE:

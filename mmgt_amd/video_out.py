@@ -42,6 +42,38 @@ def frames_uint8(videos, n_rows=6) -> np.ndarray:
     return grid
 
 
+def _clip(frames, who, empty=True, max_side=None, a_frame="a frame", strip_rows=False, default_rows=None):
+    """The common opening of the encode_*_frames functions, in `who`'s name: frames must be uint8 (n, H, W, 3); unless empty=False an empty clip is
+    refused; max_side limits H and W; strip_rows (False: the function has none) defaults to default_rows, must be at least 1 and is clamped to H.
+    -> (the frames as a tensor, where they were; n, H, W, strip_rows).  _on_device uploads them: whatever else a function checks stands between the
+    two, so that every bad argument is refused on a host without a GPU."""
+    x = torch.as_tensor(frames)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
+        raise ValueError(f"{who}: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
+    n, H, W, _ = x.shape
+    if empty and (n == 0 or H == 0 or W == 0):
+        raise ValueError(f"{who}: empty clip {tuple(x.shape)}")
+    if max_side is not None and (H > max_side or W > max_side):
+        raise ValueError(f"{who}: {a_frame} is at most {max_side} x {max_side}, got {W} x {H}")
+    if strip_rows is not False:
+        strip_rows = int(default_rows if strip_rows is None else strip_rows)
+        if strip_rows < 1:
+            raise ValueError(f"{who}: strip_rows must be at least 1, got {strip_rows}")
+        strip_rows = min(strip_rows, H)
+    return x, n, H, W, strip_rows
+
+
+def _on_device(x):
+    return (x if x.is_cuda else x.cuda()).contiguous()
+
+
+def _batches(x, scratch_bytes, per_frame):
+    """The clip in the parts that one set of launches takes: as many frames as scratch_bytes hold at per_frame bytes each, one at least."""
+    per_call = max(1, scratch_bytes // per_frame)
+    for f0 in range(0, x.shape[0], per_call):
+        yield x[f0:f0 + per_call]
+
+
 # ---- JFIF headers: everything of a frame's file that does not depend on its pixels (T.81 Annex B, JFIF 1.01) ----------------------------------
 # T.81 Annex K.3 BITS / HUFFVAL of the four standard Huffman tables (the same tables csrc/mjpeg.hip codes with)
 _DC_BITS = (bytes([0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0]), bytes([0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0]))
@@ -85,21 +117,14 @@ def encode_jpeg_frames(frames, quality=90, subsampling="4:2:0") -> list:
     Colour transform, DCT, quantiser, Huffman coding, byte stuffing and compaction run on the device (csrc/mjpeg.hip); the host receives the
     offsets and ONE buffer of scan data and prepends the fixed headers.  The bytes are the same on every call."""
     from . import hip
-    x = torch.as_tensor(frames)
-    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError(f"encode_jpeg_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
-    if not x.is_cuda:
-        x = x.cuda()
-    x = x.contiguous()
-    n, H, W, _ = x.shape
+    x, n, H, W, _ = _clip(frames, "encode_jpeg_frames", empty=False)
+    x = _on_device(x)
     if n == 0:
         return []
     head = jfif_headers(W, H, quality, subsampling)                          # also the argument check: the library refuses bad ones
     rows = hip.jpeg_geometry(H, W, subsampling)[0]
-    per_call = max(1, JPEG_SCRATCH_BYTES // (rows * hip.jpeg_segment_stride(W, subsampling)))
     out = []
-    for f0 in range(0, n, per_call):
-        part = x[f0:f0 + per_call]
+    for part in _batches(x, JPEG_SCRATCH_BYTES, rows * hip.jpeg_segment_stride(W, subsampling)):
         segs, sizes = hip.jpeg_entropy(hip.jpeg_dct_quant(part, quality, subsampling), H, W, subsampling)
         data, off = hip.jpeg_compact(segs, sizes, rows)
         data = data.cpu().numpy().tobytes()
@@ -278,33 +303,19 @@ def encode_gif_frames(frames_u8, palette=None, strip_rows=None):
     builds palette and lookup table from the 128 KB histogram (gif_palette / gif_lut, skipped for the histogram if `palette` is given) and receives
     the sizes and ONE buffer of finished bytes per set of launches.  The bytes are the same on every call."""
     from . import hip
-    x = torch.as_tensor(frames_u8)
-    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError(f"encode_gif_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
-    n, H, W, _ = x.shape
-    if n == 0 or H == 0 or W == 0:
-        raise ValueError(f"encode_gif_frames: empty clip {tuple(x.shape)}")
-    if H > 65535 or W > 65535:
-        raise ValueError(f"encode_gif_frames: a GIF frame is at most 65535 x 65535, got {W} x {H}")
+    x, n, H, W, strip_rows = _clip(frames_u8, "encode_gif_frames", max_side=65535, a_frame="a GIF frame", strip_rows=strip_rows,
+                                   default_rows=GIF_STRIP_ROWS)
     if palette is not None:
         palette = _gif_check_palette(palette).copy()
-    strip_rows = int(GIF_STRIP_ROWS if strip_rows is None else strip_rows)
-    if strip_rows < 1:
-        raise ValueError(f"encode_gif_frames: strip_rows must be at least 1, got {strip_rows}")
-    strip_rows = min(strip_rows, H)
-    if not x.is_cuda:
-        x = x.cuda()
-    x = x.contiguous()
+    x = _on_device(x)
     if palette is None:
         palette = gif_palette(hip.gif_histogram(x).cpu().numpy().view(np.uint32))
     lut = torch.from_numpy(gif_lut(palette)).to(x.device)
     strips = -(-H // strip_rows)
     stride = hip.gif_strip_stride(W, strip_rows)
-    per_frame = H * W + strips * stride + hip.gif_packed_stride(strips, stride)
-    per_call = max(1, GIF_SCRATCH_BYTES // per_frame)
     blobs = []
-    for f0 in range(0, n, per_call):
-        packed, sizes = hip.gif_pack(*hip.gif_lzw(hip.gif_index(x[f0:f0 + per_call], lut), strip_rows))
+    for part in _batches(x, GIF_SCRATCH_BYTES, H * W + strips * stride + hip.gif_packed_stride(strips, stride)):
+        packed, sizes = hip.gif_pack(*hip.gif_lzw(hip.gif_index(part, lut), strip_rows))
         sizes = sizes.tolist()
         if min(sizes) < 1:
             raise RuntimeError("encode_gif_frames: the packed frame did not fit its slot (mmgt_gif_pack)")
@@ -425,14 +436,17 @@ def _canonical_codes(lengths):
     return np.where(lengths > 0, _REV16[code & 0xFFFF] >> (16 - lengths), 0)
 
 
-def _rle_code_lengths(seq):
+def _rle_code_lengths(seq, prev=None):
     """The code lengths as (symbol, extra bits, extra value) of the code-length alphabet.  Zeros: 18 for min(run, 138) while 11 or more are left,
-    then 17 for 3 .. 10, then single zeros; a non-zero length: itself, then 16 for min(rest, 6) while 3 or more are left, then itself."""
+    then 17 for 3 .. 10, then single zeros.  A non-zero length equal to the one that 16 repeats, with 3 or more equal lengths from here on, is 16
+    for min(run, 6) of them; otherwise the length itself.  prev=None is RFC 1951's rule: 16 repeats the length written just before it, so a
+    non-zero length is written once and then repeated.  An integer is VP8L's rule: 16 repeats `prev`, which starts at that value (the format says
+    8) and which only a non-zero length written as itself changes."""
     seq = np.asarray(seq)
     cut = np.flatnonzero(np.diff(seq)) + 1
     starts = np.concatenate([[0], cut])
     runs = np.diff(np.concatenate([starts, [seq.size]]))
-    out = []
+    out, last = [], prev
     for v, run in zip(seq[starts].tolist(), runs.tolist()):
         if v == 0:
             while run >= 11:
@@ -442,15 +456,44 @@ def _rle_code_lengths(seq):
             if run >= 3:
                 out.append((17, 3, run - 3))
                 run = 0
-        else:
-            out.append((v, 0, 0))
-            run -= 1
-            while run >= 3:
+            out += [(0, 0, 0)] * run
+            continue
+        if prev is None:
+            last = None
+        while run:
+            if v == last and run >= 3:
                 k = min(run, 6)
                 out.append((16, 2, k - 3))
                 run -= k
-        out += [(v, 0, 0)] * run
+            else:
+                out.append((v, 0, 0))
+                last = v
+                run -= 1
     return out
+
+
+def _put_code_lengths(acc, nb, syms, order, vp8l):
+    """Appends to the LSB-first bit string (acc, nb) what describes a prefix code in deflate and in VP8L alike, given its code lengths as `syms`
+    (_rle_code_lengths): the code-length code's lengths by package-merge at limit 7 and its canonical codes; in 4 bits the count - 4 of those lengths
+    that are written, in the format's `order` with the trailing zeros trimmed, at least 4; those lengths at 3 bits each; then `syms` coded with that
+    code, each with its extra bits.  vp8l: a zero bit stands before the symbols (max_symbol is not used), and a code-length code with ONE used
+    symbol is read with zero bits per token, whatever length it states: then only the extra bits are written.  -> (acc, nb)."""
+    cl = deflate_code_lengths(np.bincount([s for s, _, _ in syms], minlength=19), 7)
+    codes = _canonical_codes(cl)
+    ncl = max(4, int(np.flatnonzero(cl[order])[-1]) + 1)
+    acc |= (ncl - 4) << nb
+    nb += 4
+    for k in range(ncl):
+        acc |= int(cl[order[k]]) << nb
+        nb += 3
+    if vp8l:
+        nb += 1
+    free = vp8l and int(np.count_nonzero(cl)) == 1
+    cl, codes = ([0] * 19, [0] * 19) if free else (cl.tolist(), codes.tolist())
+    for s, eb, ev in syms:
+        acc |= (codes[s] | ev << cl[s]) << nb
+        nb += cl[s] + eb
+    return acc, nb
 
 
 def deflate_block_header(litlen_lengths, dist_lengths, final):
@@ -462,18 +505,8 @@ def deflate_block_header(litlen_lengths, dist_lengths, final):
     if ll.size != 286 or not 1 <= dl.size <= 30 or ll[256] == 0:
         raise ValueError("deflate_block_header: 286 literal/length code lengths with symbol 256 used, and 1 .. 30 distance code lengths")
     nll = max(257, int(np.flatnonzero(ll)[-1]) + 1)
-    syms = _rle_code_lengths(np.concatenate([ll[:nll], dl]))
-    cl = deflate_code_lengths(np.bincount([s for s, _, _ in syms], minlength=19), 7)
-    codes = _canonical_codes(cl)
-    ncl = max(4, int(np.flatnonzero(cl[_CL_ORDER])[-1]) + 1)
-    acc, nb = (1 if final else 0) | 2 << 1 | (nll - 257) << 3 | (dl.size - 1) << 8 | (ncl - 4) << 13, 17
-    for k in range(ncl):
-        acc |= int(cl[_CL_ORDER[k]]) << nb
-        nb += 3
-    cl, codes = cl.tolist(), codes.tolist()
-    for s, eb, ev in syms:
-        acc |= (codes[s] | ev << cl[s]) << nb
-        nb += cl[s] + eb
+    acc, nb = (1 if final else 0) | 2 << 1 | (nll - 257) << 3 | (dl.size - 1) << 8, 13          # HCLEN and what follows it: _put_code_lengths
+    acc, nb = _put_code_lengths(acc, nb, _rle_code_lengths(np.concatenate([ll[:nll], dl])), _CL_ORDER, False)
     return acc.to_bytes((nb + 7) // 8, "little"), nb
 
 
@@ -502,29 +535,15 @@ def encode_png_frames(frames_u8, strip_rows=None) -> list:
     them, and receives the Adler-32 sums of the rows and ONE buffer of finished bytes per set of launches.  The bytes are the same on every call;
     DESIGN.md 4g defines them."""
     from . import hip
-    x = torch.as_tensor(frames_u8)
-    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError(f"encode_png_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
-    n, H, W, _ = x.shape
-    if n == 0 or H == 0 or W == 0:
-        raise ValueError(f"encode_png_frames: empty clip {tuple(x.shape)}")
-    if H > PNG_MAX_SIDE or W > PNG_MAX_SIDE:
-        raise ValueError(f"encode_png_frames: a frame is at most {PNG_MAX_SIDE} x {PNG_MAX_SIDE}, got {W} x {H}")
-    strip_rows = int(PNG_STRIP_ROWS if strip_rows is None else strip_rows)
-    if strip_rows < 1:
-        raise ValueError(f"encode_png_frames: strip_rows must be at least 1, got {strip_rows}")
-    strip_rows = min(strip_rows, H)
-    if not x.is_cuda:
-        x = x.cuda()
-    x = x.contiguous()
+    x, n, H, W, strip_rows = _clip(frames_u8, "encode_png_frames", max_side=PNG_MAX_SIDE, strip_rows=strip_rows, default_rows=PNG_STRIP_ROWS)
+    x = _on_device(x)
     rowlen = 1 + 3 * W
     strips = -(-H // strip_rows)
     # filtered rows; slots and output, each at most 15 bits a byte and a header per strip; histograms, code tables, headers and offsets
     per_frame = 5 * H * rowlen + strips * (2 * 286 * 4 + 3 * hip.PNG_HEADER_BYTES + 64)
-    per_call = max(1, PNG_SCRATCH_BYTES // per_frame)
     blobs = []
-    for f0 in range(0, n, per_call):
-        filt, sums = hip.png_filter(x[f0:f0 + per_call])
+    for part in _batches(x, PNG_SCRATCH_BYTES, per_frame):
+        filt, sums = hip.png_filter(part)
         raw = deflate_strips_device(filt.view(filt.shape[0], H * rowlen), strip_rows * rowlen)
         for body, rows in zip(raw, sums.cpu().numpy().tolist()):
             adler = 1
@@ -646,45 +665,13 @@ _WEBP_GREEN_EXTRA = np.zeros(280, np.int64)
 _WEBP_GREEN_EXTRA[260:] = np.arange(4, 24) // 2 - 1
 
 
-def _webp_rle_code_lengths(seq):
-    """The code lengths as (symbol, extra bits, extra value) of VP8L's code-length alphabet.  Zeros: 18 for min(run, 138) while 11 or more are left,
-    then 17 for 3 .. 10, then single zeros.  `prev` starts at 8 and only a length written as itself changes it: a non-zero length equal to prev with
-    3 or more equal lengths from here on is 16 for min(run, 6) of them; otherwise the length itself."""
-    seq = np.asarray(seq)
-    cut = np.flatnonzero(np.diff(seq)) + 1
-    starts = np.concatenate([[0], cut])
-    runs = np.diff(np.concatenate([starts, [seq.size]]))
-    out, prev = [], 8
-    for v, run in zip(seq[starts].tolist(), runs.tolist()):
-        if v == 0:
-            while run >= 11:
-                k = min(run, 138)
-                out.append((18, 7, k - 11))
-                run -= k
-            if run >= 3:
-                out.append((17, 3, run - 3))
-                run = 0
-            out += [(0, 0, 0)] * run
-            continue
-        while run:
-            if v == prev and run >= 3:
-                k = min(run, 6)
-                out.append((16, 2, k - 3))
-                run -= k
-            else:
-                out.append((v, 0, 0))
-                prev = v
-                run -= 1
-    return out
-
-
 def webp_prefix_code(counts):
     """Counts per symbol of one alphabet -> (lengths as the pixels are coded with them, the code's description as an LSB-first bit string, its bit
     count).  One used symbol (below 256), or none (then symbol 0): a simple code, bits 1 0 and 0 + 1 bit or 1 + 8 bits of symbol, and the symbol
     costs NO bits, so the lengths are all zero.  Otherwise a normal code: bit 0, the count of code-length-code lengths - 4 (trailing zeros in
     VP8L's order trimmed, at least 4), those lengths at 3 bits each, bit 0 (max_symbol is not used), then the alphabet's lengths
-    (deflate_code_lengths, limit 15) run-length coded (_webp_rle_code_lengths) with the code-length code (limit 7).  A code-length code with ONE used
-    symbol is read with zero bits per token, whatever length it states: then only the extra bits are written."""
+    (deflate_code_lengths, limit 15) run-length coded (_rle_code_lengths with prev = 8) with the code-length code (limit 7): _put_code_lengths.  A
+    code-length code with ONE used symbol is read with zero bits per token, whatever length it states: then only the extra bits are written."""
     h = np.asarray(counts).astype(np.int64).reshape(-1)
     used = np.flatnonzero(h)
     if used.size <= 1:
@@ -694,20 +681,7 @@ def webp_prefix_code(counts):
         acc, nb = (0b01 | 0 << 2 | s << 3, 4) if s < 2 else (0b01 | 1 << 2 | s << 3, 11)
         return np.zeros(h.size, np.int64), acc, nb
     lengths = deflate_code_lengths(h, 15)
-    syms = _webp_rle_code_lengths(lengths)
-    cl = deflate_code_lengths(np.bincount([s for s, _, _ in syms], minlength=19), 7)
-    codes = _canonical_codes(cl)
-    ncl = max(4, int(np.flatnonzero(cl[_WEBP_CL_ORDER])[-1]) + 1)
-    one = int(np.count_nonzero(cl)) == 1
-    acc, nb = (ncl - 4) << 1, 5
-    for k in range(ncl):
-        acc |= int(cl[_WEBP_CL_ORDER[k]]) << nb
-        nb += 3
-    nb += 1
-    cl, codes = ([0] * 19, [0] * 19) if one else (cl.tolist(), codes.tolist())
-    for s, eb, ev in syms:
-        acc |= (codes[s] | ev << cl[s]) << nb
-        nb += cl[s] + eb
+    acc, nb = _put_code_lengths(0, 1, _rle_code_lengths(lengths, prev=8), _WEBP_CL_ORDER, True)   # bit 0: a normal code
     return lengths, acc, nb
 
 
@@ -783,29 +757,15 @@ def encode_webp_frames(frames_u8, strip_rows=None) -> list:
     builds each frame's five codes and its header from the device's block modes and symbol histograms, knows every strip's bit count from them,
     and receives ONE buffer of finished bytes per set of launches.  The bytes are the same on every call; DESIGN.md 4j defines them."""
     from . import hip
-    x = torch.as_tensor(frames_u8)
-    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError(f"encode_webp_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
-    n, H, W, _ = x.shape
-    if n == 0 or H == 0 or W == 0:
-        raise ValueError(f"encode_webp_frames: empty clip {tuple(x.shape)}")
-    if H > WEBP_MAX_SIDE or W > WEBP_MAX_SIDE:
-        raise ValueError(f"encode_webp_frames: a frame is at most {WEBP_MAX_SIDE} x {WEBP_MAX_SIDE}, got {W} x {H}")
-    strip_rows = int(WEBP_STRIP_ROWS if strip_rows is None else strip_rows)
-    if strip_rows < 1:
-        raise ValueError(f"encode_webp_frames: strip_rows must be at least 1, got {strip_rows}")
-    strip_rows = min(strip_rows, H)
-    if not x.is_cuda:
-        x = x.cuda()
-    x = x.contiguous()
+    x, n, H, W, strip_rows = _clip(frames_u8, "encode_webp_frames", max_side=WEBP_MAX_SIDE, strip_rows=strip_rows, default_rows=WEBP_STRIP_ROWS)
+    x = _on_device(x)
     strips = -(-H // strip_rows)
     blocks = -(-H >> WEBP_PREDICTOR_BITS) * -(-W >> WEBP_PREDICTOR_BITS)
     # residual words; slots and output, each at most 45 bits a pixel; the header with its modes; histograms and offsets
     per_frame = 4 * H * W + 2 * 6 * H * W + 3 * (blocks + 2048) + strips * (793 * 4 + 64) + 792 * 4
-    per_call = max(1, WEBP_SCRATCH_BYTES // per_frame)
     blobs = []
-    for f0 in range(0, n, per_call):
-        modes, res = hip.webp_predict(x[f0:f0 + per_call])
+    for part in _batches(x, WEBP_SCRATCH_BYTES, per_frame):
+        modes, res = hip.webp_predict(part)
         k = res.shape[0]
         data = res.view(k, H * W)
         hist = hip.webp_histogram(data, strip_rows * W).cpu().numpy().view(np.uint32).astype(np.int64)          # (k, strips, 793)
@@ -846,14 +806,7 @@ def encode_vp8_frames(frames_u8, quality=75, partitions=None, filter_level=None)
     2, 4 or 8 (None: vp8_default_partitions); filter_level 0 .. 63 is the loop filter level the decoder applies (None: the default of the quantiser
     index; 0 makes the decode equal the encoder's reconstruction).  The bytes are the same on every call; DESIGN.md 4l defines them."""
     from . import hip
-    x = torch.as_tensor(frames_u8)
-    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3:
-        raise ValueError(f"encode_vp8_frames: expected uint8 (n, H, W, 3), got {x.dtype} {tuple(x.shape)}")
-    n, H, W, _ = x.shape
-    if n == 0 or H == 0 or W == 0:
-        raise ValueError(f"encode_vp8_frames: empty clip {tuple(x.shape)}")
-    if H > VP8_MAX_SIDE or W > VP8_MAX_SIDE:
-        raise ValueError(f"encode_vp8_frames: a frame is at most {VP8_MAX_SIDE} x {VP8_MAX_SIDE}, got {W} x {H}")
+    x, n, H, W, _ = _clip(frames_u8, "encode_vp8_frames", max_side=VP8_MAX_SIDE)
     quality = int(quality)
     if not 0 <= quality <= 100:
         raise ValueError(f"encode_vp8_frames: quality must be 0 .. 100, got {quality}")
@@ -864,17 +817,13 @@ def encode_vp8_frames(frames_u8, quality=75, partitions=None, filter_level=None)
     filter_level = level if filter_level is None else int(filter_level)
     if not 0 <= filter_level <= 63:
         raise ValueError(f"encode_vp8_frames: filter_level must be 0 .. 63, got {filter_level}")
-    if not x.is_cuda:
-        x = x.cuda()
-    x = x.contiguous()
+    x = _on_device(x)
     mbs = -(-H // 16) * -(-W // 16)
     first, token = hip.vp8_slot_bytes(H, W, partitions)
     # source and reconstructed planes, levels, modes and masks; the worst-case slots; the packed frames are never longer than the slots
     per_frame = 2 * 384 * mbs + (800 + 6) * mbs + 2 * (first + partitions * token) + 64
-    per_call = max(1, VP8_SCRATCH_BYTES // per_frame)
     blobs = []
-    for f0 in range(0, n, per_call):
-        part = x[f0:f0 + per_call]
+    for part in _batches(x, VP8_SCRATCH_BYTES, per_frame):
         _, levels, modes, nz, skipped = hip.vp8_analyse(hip.vp8_convert(part), H, W, q)
         slots, counts = hip.vp8_code(levels, nz, modes, skipped, H, W, q, partitions, filter_level)
         packed, out_off = hip.vp8_pack(slots, counts, H, W, partitions)

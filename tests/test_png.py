@@ -7,6 +7,7 @@ rounded up to the next whole percent.  The bytes are deterministic: this guards 
 import io
 import itertools
 import struct
+import subprocess
 import zlib
 from fractions import Fraction
 
@@ -16,6 +17,8 @@ import torch
 from PIL import Image
 
 from tests import png_ref as R
+from tests.host_check import host_check  # noqa: F401  (the fixture)
+from tests.test_png_gpu import _crafted
 
 SIZE_RATIO_GATE = 1.03
 
@@ -255,3 +258,24 @@ def test_bad_arguments_raise(tmp_path):
         V.write_png(p, blob[0], 4, 16385)
     with pytest.raises(ValueError):
         V.write_png_sequence(str(tmp_path / "d"), [], 4, 4)
+
+
+# ---- the product's tokens in a host program under ASan + UBSan -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", sorted(_crafted()))
+def test_host_program_tokens_equal_the_yardstick(host_check, tmp_path, case):
+    """csrc/strip_coder.h's closed form at 258, the tokens of csrc/png.hip, on the device tests' crafted buffers: every strip's tokens are the
+    yardstick's greedy parse."""
+    data, strip_bytes = _crafted()[case]
+    rows = 2 if case == "two_rows" else 1
+    for row in np.frombuffer(data, np.uint8).reshape(rows, -1):
+        row = row.tobytes()
+        job, out = tmp_path / "job.bin", tmp_path / "out.bin"
+        job.write_bytes(struct.pack("<2i", len(row), strip_bytes) + row)
+        r = subprocess.run([host_check, "--png-tokens", str(job), str(out)], capture_output=True, text=True)
+        assert r.returncode == 0, f"{r.stdout[-500:]}{r.stderr[-3000:]}"
+        got, at = np.frombuffer(out.read_bytes(), np.uint32).tolist(), 0
+        for first in range(0, len(row), strip_bytes):
+            want = [v if kind == "lit" else v | 0x1000 for kind, v in R.tokens(row[first:first + strip_bytes])]
+            assert got[at] == len(want) and got[at + 1:at + 1 + got[at]] == want, (case, first)
+            at += 1 + got[at]
+        assert at == len(got)

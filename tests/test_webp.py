@@ -5,7 +5,6 @@ host program built with AddressSanitizer and UBSan, where its modes, residuals a
 tolerance except the stream-size ratios, which are held to what was measured."""
 import io
 import os
-import shutil
 import struct
 import subprocess
 
@@ -15,6 +14,7 @@ from PIL import Image
 
 from tests import png_ref as P
 from tests import webp_ref as R
+from tests.host_check import host_check  # noqa: F401  (the fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((37, 29), (1, 1), (300, 1), (1, 300), (16, 17), (17, 16), (33, 47))              # W x H
@@ -256,7 +256,7 @@ def test_product_rle_equals_the_yardsticks():
     seqs = [[8] * 20, [8, 8], [8, 8, 8], [7] * 9 + [8] * 4, [0] * 150 + [3, 3, 3, 3, 0, 0, 0, 5], [0] * 10 + [1] + [0] * 11 + [1] * 7 + [0, 0], [5]]
     seqs += [rng.choice([0, 0, 0, 4, 8, 8, 9], 280).tolist() for _ in range(20)]
     for seq in seqs:
-        assert V._webp_rle_code_lengths(seq) == R.rle_code_lengths(seq), seq
+        assert V._rle_code_lengths(seq, prev=8) == R.rle_code_lengths(seq), seq
     with pytest.raises(ValueError, match="simple code"):
         V.webp_prefix_code([0] * 256 + [4] + [0] * 23)
 
@@ -288,18 +288,6 @@ def test_stream_size_against_pil_and_png(kind):
 
 
 # ---- the product's arithmetic in a host program under ASan + UBSan ------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def host_check(tmp_path_factory):
-    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
-    assert cxx, "no host C++ compiler (g++ / clang++) to build tools/webp_host_check.cpp with"
-    exe = tmp_path_factory.mktemp("webp_host") / "webp_host_check"
-    cmd = [cxx, "-std=c++20", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "mmgt_amd", "csrc"),
-           os.path.join(ROOT, "tools", "webp_host_check.cpp"), "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-4000:]
-    return str(exe)
-
-
 def host_run(exe, tmp_path, frames, strip_rows):
     frames = np.ascontiguousarray(frames)
     n, H, W, _ = frames.shape

@@ -2,14 +2,20 @@
 // be built with AddressSanitizer and UBSan and held to the yardstick of tests/webp_ref.py without a GPU (tests/test_webp.py builds and runs it).
 //
 //   webp_host_check JOB OUT
+//   webp_host_check --png-tokens JOB OUT
 //
 // JOB: int32 n, H, W, strip_rows, then n * H * W * 3 bytes of RGB.  OUT: the modes, n * bh * bw bytes; the residuals, n * H * W uint32 ARGB words;
 // then per frame and strip an uint32 count of tokens and per token two uint32: 0 and the literal's word, or a match's length and its prefix symbol |
 // extra bits << 8 | extra value << 16.  The loops mirror the kernels': a block's 14 costs summed pixel by pixel, the residuals taken under the
 // winning mode, a strip's tokens found position by position from the start of the run that the position lies in.
+//
+// --png-tokens runs the PNG writer's tokens (csrc/png.hip: csrc/strip_coder.h's closed form at 258, which webp_core.h's wp_token_at uses at 4096) the
+// same way (tests/test_png.py).  JOB: int32 len, strip_bytes, then len bytes.  OUT: per strip an uint32 count of tokens and per token one uint32, the
+// literal's byte or a match's length | 0x1000.  The end-of-block symbol is not a token of the closed form and is not written.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "webp_core.h"
@@ -19,8 +25,39 @@ static int fail(const char* what) {
   return 2;
 }
 
+static int png_tokens(const char* job, const char* result) {
+  FILE* in = std::fopen(job, "rb");
+  if (!in) return fail("cannot open the job");
+  int32_t head[2];
+  if (std::fread(head, sizeof(int32_t), 2, in) != 2) return fail("short job");
+  const long len = head[0], strip_bytes = head[1];
+  if (len < 1 || len > (1l << 26) || strip_bytes < 1) return fail("sizes outside the range");
+  std::vector<unsigned char> data((size_t)len);
+  if (std::fread(data.data(), 1, data.size(), in) != data.size()) return fail("short job");
+  std::fclose(in);
+  FILE* out = std::fopen(result, "wb");
+  if (!out) return fail("cannot open the output");
+  for (long first = 0; first < len; first += strip_bytes) {
+    const int n = (int)(len - first < strip_bytes ? len - first : strip_bytes);
+    std::vector<unsigned char> strip(data.begin() + first, data.begin() + first + n);                           // its own allocation: ASan sees its ends
+    std::vector<uint32_t> toks;
+    int run_start = 0;
+    for (int p = 0; p < n; ++p) {
+      if (p > 0 && strip[(size_t)p] != strip[(size_t)p - 1]) run_start = p;
+      const int tok = sc_token_at<258>(ScSameAsBefore<unsigned char>{strip.data()}, p, n, run_start);
+      if (tok != SC_NONE) toks.push_back(tok == SC_LITERAL ? (uint32_t)strip[(size_t)p] : (uint32_t)tok | 0x1000u);
+    }
+    const uint32_t count = (uint32_t)toks.size();
+    std::fwrite(&count, sizeof(uint32_t), 1, out);
+    std::fwrite(toks.data(), sizeof(uint32_t), toks.size(), out);
+  }
+  if (std::fclose(out) != 0) return fail("cannot write the output");
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  if (argc != 3) return fail("usage: webp_host_check JOB OUT");
+  if (argc == 4 && std::string(argv[1]) == "--png-tokens") return png_tokens(argv[2], argv[3]);
+  if (argc != 3) return fail("usage: webp_host_check [--png-tokens] JOB OUT");
   FILE* in = std::fopen(argv[1], "rb");
   if (!in) return fail("cannot open the job");
   int32_t head[4];
