@@ -278,6 +278,25 @@ int mmgt_silu(const void* x, void* out, long n, int dtype, void* stream);
 int mmgt_cfg_ddim_step(const float* pred_sum, const float* counter, const float* latents, float* latents_out, long n,
                        int F, int hw, float guidance, float sa_t, float sb_t, float sa_p, float sb_p, void* stream);
 
+/* The sampler's general update (csrc/sampler.hip): with eps_u, eps_c and v_g = eps_u + s (eps_c - eps_u) formed exactly as mmgt_cfg_ddim_step forms
+ * them,
+ *   rho = rescale sqrt(Var eps_c / Var v_g) + (1 - rescale)   (variances over all n elements; rho = 1 and `moments` unread when rescale == 0)
+ *   v = rho v_g;   x0 = sa_t x - sb_t v;   x_next = k_x x + k_0 x0 + k_1 prev_x0 + k_v v + k_z noise
+ * prev_x0 and noise may be null (their terms are skipped; a non-zero k_1 / k_z without its tensor is refused); x0 is also written to x0_out
+ * when that is not null.  rescale outside [0, 1] is refused.  The coefficients: mmgt_amd/scheduler.py `update_coefficients` (DDIM with
+ * eta > 0: diffusers DDIMScheduler.step; DPM-Solver++ 2M: Lu et al. 2211.01095 Alg. 2).
+ * Replaces: rescale_noise_cfg of src/pipelines/pipeline_lmks2vid_long.py + scheduler.step(..., eta) of pipeline_pose2vid_long.py:627-635. */
+int mmgt_sampler_step(const float* pred_sum, const float* counter, const float* latents, const float* prev_x0, const float* noise,
+                      const double* moments, float* latents_out, float* x0_out, long n, int F, int hw, float guidance, float rescale, float sa_t,
+                      float sb_t, float k_x, float k_0, float k_1, float k_v, float k_z, void* stream);
+
+/* moments[4] (fp64, device) = (sum eps_c, sum eps_c^2, sum v_g, sum v_g^2) over the n elements, for mmgt_sampler_step's rho: no host
+ * synchronisation.  Summed in fp64 in a fixed order -- per workgroup into partials[blocks][4], blocks a function of n alone (at most 512 =
+ * the partials_rows that always suffice), then folded by one workgroup in index order; no atomics -- so equal inputs give equal bits on
+ * every launch and every rank. */
+int mmgt_cfg_moments(const float* pred_sum, const float* counter, long n, int F, int hw, float guidance, double* partials, int partials_rows,
+                     double* moments, void* stream);
+
 /* pred_sum[:, :, idx[j]] += pred[:, :, j]; counter[idx[j]] += 1 for a window of Fw frames (closed-loop indices).
  * pred is channels-last T ((2*Fw), hw, Cpad) as produced by the UNet; pred_sum fp32 (2, C, F, hw).
  * Replaces: src/pipelines/pipeline_pose2vid_long.py:622-624. */

@@ -93,6 +93,9 @@ _SIGS = {
     "mmgt_silu": (c_int, [c_void_p, c_void_p, c_long, c_int, c_void_p]),
     "mmgt_cfg_ddim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_float,
                                    c_float, c_float, c_float, c_void_p]),
+    "mmgt_sampler_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_float,
+                                  c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p]),
+    "mmgt_cfg_moments": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
     "mmgt_accumulate_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p]),
     "mmgt_rotary": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
@@ -894,6 +897,75 @@ def cfg_ddim_step(pred_sum, counter, latents, guidance, sa_t, sb_t, sa_p, sb_p, 
     _check(lib().mmgt_cfg_ddim_step(_ptr(pred_sum), _ptr(_f32(counter, "counter")), _ptr(latents), _ptr(out),
                                     latents.numel(), F, H * W, guidance, sa_t, sb_t, sa_p, sb_p, _stream()),
            "mmgt_cfg_ddim_step")
+    return out
+
+
+MOMENT_PARTIAL_ROWS = 512          # rows of per-workgroup partial sums that mmgt_cfg_moments never exceeds (include/mmgt_hip.h)
+
+
+def _cfg_shapes(what, pred_sum, counter, lat_shape):
+    """the refusals of `cfg_ddim_step` for the entries of csrc/sampler.hip: pred_sum float32 (2, C, F, H, W) for latents (1, C, F, H, W), counter
+    float32 (F,).  -> (n, F, hw)"""
+    if len(lat_shape) != 5 or lat_shape[0] != 1:
+        raise RuntimeError(f"{what}: latents must be (1, C, F, H, W), got {tuple(lat_shape)}")
+    if pred_sum.dtype != torch.float32 or tuple(pred_sum.shape) != (2,) + tuple(lat_shape[1:]) or not pred_sum.is_contiguous():
+        raise RuntimeError(f"{what}: pred_sum must be contiguous float32 {(2,) + tuple(lat_shape[1:])}, got {pred_sum.dtype} {tuple(pred_sum.shape)}")
+    _, C, F, H, W = lat_shape
+    if counter.numel() != F:
+        raise RuntimeError(f"{what}: counter has {counter.numel()} entries for {F} frames")
+    _f32(counter, "counter")
+    return C * F * H * W, F, H * W
+
+
+def cfg_moments(pred_sum, counter, guidance, out=None):
+    """pred_sum (2, C, F, H, W) fp32, counter (F,) fp32 -> fp64 (4,) on the device: (sum v_c, sum v_c^2, sum v_g, sum v_g^2) over the C F H W elements
+    of v_c = pred_sum[1] / counter and v_g = v_u + guidance (v_c - v_u), in a fixed order (bit-equal from launch to launch).  No host sync."""
+    _dev(pred_sum, counter, out)
+    if pred_sum.dim() != 5:
+        raise RuntimeError(f"cfg_moments: pred_sum must be (2, C, F, H, W), got {tuple(pred_sum.shape)}")
+    n, F, hw = _cfg_shapes("cfg_moments", pred_sum, counter, (1,) + tuple(pred_sum.shape[1:]))
+    if out is None:
+        out = torch.empty((4,), device=pred_sum.device, dtype=torch.float64)
+    if out.dtype != torch.float64 or tuple(out.shape) != (4,) or not out.is_contiguous():
+        raise RuntimeError(f"cfg_moments: out must be contiguous float64 (4,), got {out.dtype} {tuple(out.shape)}")
+    part = torch.empty((MOMENT_PARTIAL_ROWS, 4), device=pred_sum.device, dtype=torch.float64)
+    _check(lib().mmgt_cfg_moments(_ptr(pred_sum), _ptr(counter), n, F, hw, guidance, _ptr(part), MOMENT_PARTIAL_ROWS, _ptr(out), _stream()),
+           "mmgt_cfg_moments")
+    return out
+
+
+def sampler_step(pred_sum, counter, latents, guidance, sa_t, sb_t, k_x, k_0, k_1, k_v, k_z, *, rescale=0.0, moments=None, prev_x0=None, noise=None,
+                 x0_out=None, out=None):
+    """The general update behind the window accumulation (include/mmgt_hip.h: mmgt_sampler_step): latents (1, C, F, H, W) fp32, pred_sum and counter as
+    for `cfg_ddim_step`; prev_x0 / noise / x0_out None or latents' shape -> new latents.
+        v = rho (v_u + guidance (v_c - v_u));  x0 = sa_t x - sb_t v;  new = k_x x + k_0 x0 + k_1 prev_x0 + k_v v + k_z noise;  x0_out = x0
+    rescale > 0: rho from `moments` (fp64 (4,) of `cfg_moments`; computed here when None).  Every refusal is raised before anything is launched."""
+    _dev(pred_sum, counter, latents, moments, prev_x0, noise, x0_out, out)
+    n, F, hw = _cfg_shapes("sampler_step", pred_sum, counter, tuple(latents.shape))
+    if latents.dtype != torch.float32 or not latents.is_contiguous():
+        raise RuntimeError(f"sampler_step: latents must be contiguous float32, got {latents.dtype}")
+    if not 0.0 <= float(rescale) <= 1.0:
+        raise RuntimeError(f"sampler_step: rescale must lie in [0, 1], got {rescale}")
+    if out is None:
+        out = torch.empty_like(latents)
+    for name, t in (("prev_x0", prev_x0), ("noise", noise), ("x0_out", x0_out), ("out", out)):
+        if t is not None and (t.shape != latents.shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError(f"sampler_step: {name} must be contiguous float32 {tuple(latents.shape)} like latents, got {t.dtype} {tuple(t.shape)}")
+    if k_1 != 0.0 and prev_x0 is None:
+        raise RuntimeError("sampler_step: k_1 != 0 (a second-order step) needs prev_x0")
+    if k_z != 0.0 and noise is None:
+        raise RuntimeError("sampler_step: k_z != 0 (eta > 0) needs noise")
+    if x0_out is not None and any(t is not None and t.data_ptr() == x0_out.data_ptr() for t in (prev_x0, out, latents)):
+        raise RuntimeError("sampler_step: x0_out must be a buffer of its own (not prev_x0, latents or out)")
+    if moments is not None and (moments.dtype != torch.float64 or tuple(moments.shape) != (4,) or not moments.is_contiguous()):
+        raise RuntimeError(f"sampler_step: moments must be contiguous float64 (4,), got {moments.dtype} {tuple(moments.shape)}")
+    if rescale > 0.0 and moments is None:
+        moments = cfg_moments(pred_sum, counter, guidance)
+    # a tensor whose coefficient is zero is not handed over: its term is skipped, whatever an unused buffer holds
+    _check(lib().mmgt_sampler_step(_ptr(pred_sum), _ptr(counter), _ptr(latents), _ptr(prev_x0 if k_1 != 0.0 else None),
+                                   _ptr(noise if k_z != 0.0 else None), _ptr(moments if rescale > 0.0 else None),
+                                   _ptr(out), _ptr(x0_out), n, F, hw, guidance, rescale, sa_t, sb_t, k_x, k_0, k_1, k_v, k_z, _stream()),
+           "mmgt_sampler_step")
     return out
 
 

@@ -9,6 +9,8 @@ Extensions through **kwargs (allowed by the reference signature, :365): `latents
 `clip_image_embeds=` / `ref_image_latents=` / `reference_banks=` / `pose_features=` (hand over prologue results when the module
 is None), `decode=False`, `window_group=` / `cfg_split=` (window-parallel sampling of one long video over several GPUs).
 `context_batch_size=B` runs the window loop B windows per forward: the same sampler as B = 1 (see `denoise`).
+`eta` (the reference's extra_step_kwargs), `guidance_rescale=` (rescale_noise_cfg of pipeline_lmks2vid_long.py) and a
+`DPMSolverMultistepScheduler` as `scheduler` select the update behind the accumulation (see `denoise`); the defaults are the reference's DDIM.
 `ref_image` may be a uint8 (h, w, 3) RGB tensor instead of a PIL image: the Lanczos resize in front of the VAE and the bicubic 224 x 224 resize
 in front of CLIP then run on the device (mmgt_amd.inputs.ref_image_tensors_device), with PIL's bytes.
 `output_type="uint8"` returns the frames as uint8 (b, f, H, W, 3), converted on the device (what save_videos_grid writes).
@@ -140,11 +142,28 @@ class Pose2VideoPipeline:
             return p5
         return hip.ncfhw_to_nhwc(p5, p5.shape[1], unet.dtype)
 
+    def _check_update_args(self, eta, guidance_rescale, window_group):
+        """The refusals of the update's arguments (each names both parties); -> whether the scheduler is the multistep solver."""
+        from .scheduler import DPMSolverMultistepScheduler
+        dpm = isinstance(self.scheduler, DPMSolverMultistepScheduler)
+        if eta < 0.0:
+            raise ValueError(f"eta must not be negative, got eta={eta}")
+        if eta > 0.0 and dpm:
+            raise ValueError(f"eta={eta} is not combined with scheduler=DPMSolverMultistepScheduler (DPM-Solver++ 2M is deterministic): use "
+                             "eta=0 or a DDIMScheduler")
+        if eta > 0.0 and window_group is not None:
+            raise ValueError(f"eta={eta} is not combined with window_group (every rank would draw its own noise and the latents would part): "
+                             "use eta=0 or one GPU")
+        if not 0.0 <= guidance_rescale <= 1.0:
+            raise ValueError(f"guidance_rescale must lie in [0, 1] (it blends the rescaled guidance_scale prediction with the plain one), got "
+                             f"guidance_rescale={guidance_rescale}")
+        return dpm
+
     # --------------------------------------------------------------------------------------------- the hot loop
     def denoise(self, latents, timesteps, encoder_hidden_states, pose_fea, audio_tensor_pre, full_masks, face_masks,
                 lip_masks, guidance_scale, motion_scale, context_frames, context_stride, context_overlap,
                 context_schedule="uniform", num_inference_steps=None, callback=None, callback_steps=1,
-                window_group=None, cfg_split="auto", context_batch_size=1):
+                window_group=None, cfg_split="auto", context_batch_size=1, eta=0.0, guidance_rescale=0.0, generator=None):
         """pipeline_pose2vid_long.py:494-643.  latents (1, C, L, h, w) fp32 on the GPU; returns the final latents.
 
         window_group: a torch.distributed process group (or True for the default group) turns on window-parallel sampling of
@@ -160,7 +179,17 @@ class Pose2VideoPipeline:
         [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)], and the predictions are added to pred_sum / counter window by window in list
         order (hip.accumulate_windows), so the fp32 accumulation order of the overlap average is that of B = 1.  Only the rounding inside the
         UNet may differ (dispatch picks tiles by the row count).  The reference's own handling of the argument is inconsistent (App. C-7)
-        and is not reproduced.  Not combined with window_group: raises ValueError."""
+        and is not reproduced.  Not combined with window_group: raises ValueError.
+
+        The update behind the accumulation follows the scheduler's class.  A DDIMScheduler with eta = 0 and guidance_rescale = 0 is
+        hip.cfg_ddim_step, as ever.  Anything else is hip.sampler_step: eta > 0 draws one fp32 noise tensor per step from `generator` (after the
+        initial latents, in step order); guidance_rescale > 0 scales the guided prediction to the conditional one's standard deviation (the
+        moments stay on the device); a DPMSolverMultistepScheduler hands every step's x0 to the next through two buffers allocated here.  All of
+        it runs after the gather, so it combines with window_group and context_batch_size -- except eta > 0 with window_group."""
+        eta, guidance_rescale = float(eta), float(guidance_rescale)
+        dpm = self._check_update_args(eta, guidance_rescale, window_group)
+        general = dpm or eta != 0.0 or guidance_rescale != 0.0
+        x0_bufs = [torch.empty_like(latents), torch.empty_like(latents)] if dpm else None
         B = int(context_batch_size)
         if B < 1:
             raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
@@ -293,8 +322,17 @@ class Pose2VideoPipeline:
                             w, row = units[u0 + r]
                             hip.accumulate_window(preds[r], pred_sum, counter, win_idx[w], C, rows=rows, row0=row or 0,
                                                   bump_counter=row in (None, 0))
-            sa_t, sb_t, sa_p, sb_p = self.scheduler.step_coefficients(t)
-            latents = hip.cfg_ddim_step(pred_sum, counter, latents, float(guidance_scale), sa_t, sb_t, sa_p, sb_p)
+            if not general:
+                sa_t, sb_t, sa_p, sb_p = self.scheduler.step_coefficients(t)
+                latents = hip.cfg_ddim_step(pred_sum, counter, latents, float(guidance_scale), sa_t, sb_t, sa_p, sb_p)
+            else:
+                noise = None
+                if eta > 0.0:                                    # on the generator's device, as the initial latents (prepare_latents)
+                    gdev = generator.device if isinstance(generator, torch.Generator) else dev
+                    noise = torch.randn(latents.shape, generator=generator, device=gdev, dtype=torch.float32).to(dev)
+                latents = hip.sampler_step(pred_sum, counter, latents, float(guidance_scale), *self.scheduler.update_coefficients(t, eta),
+                                           rescale=guidance_rescale, noise=noise, prev_x0=x0_bufs[(i - 1) % 2] if dpm and i > 0 else None,
+                                           x0_out=x0_bufs[i % 2] if dpm else None)
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
         return latents
@@ -307,9 +345,8 @@ class Pose2VideoPipeline:
                  generator=None, output_type: Optional[str] = "tensor", return_dict: bool = True,
                  callback: Optional[Callable] = None, callback_steps: Optional[int] = 1, context_schedule="uniform",
                  context_frames=12, context_stride=1, context_overlap=4, context_batch_size=1, interpolation_factor=1,
-                 **kwargs):
-        if eta != 0.0:
-            raise NotImplementedError("eta != 0 is not used by the reference scripts")
+                 guidance_rescale: float = 0.0, **kwargs):
+        self._check_update_args(float(eta), float(guidance_rescale), kwargs.get("window_group"))
         if int(context_batch_size) < 1:
             raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
         if not guidance_scale > 1.0:
@@ -376,7 +413,8 @@ class Pose2VideoPipeline:
                                lip_masks, guidance_scale, motion_scale, context_frames, context_stride, context_overlap,
                                context_schedule, num_inference_steps, callback, callback_steps,
                                window_group=kwargs.get("window_group"), cfg_split=kwargs.get("cfg_split", "auto"),
-                               context_batch_size=context_batch_size)
+                               context_batch_size=context_batch_size, eta=eta, guidance_rescale=guidance_rescale,
+                               generator=generator if isinstance(generator, torch.Generator) else None)
         unet.clear_banks()                                                                # :645-646
 
         if interpolation_factor > 0:

@@ -256,5 +256,22 @@ def _(z, weights):
     return z.new_empty((z.shape[0], 3, 8 * z.shape[2], 8 * z.shape[3]))
 
 
+@_lib.custom_op("mmgt_hip::sampler_step", mutates_args=(), device_types="cuda")
+def sampler_step(pred_sum: torch.Tensor, counter: torch.Tensor, latents: torch.Tensor, prev_x0: Optional[torch.Tensor], noise: Optional[torch.Tensor],
+                 guidance: float, rescale: float, coefficients: List[float]) -> List[torch.Tensor]:
+    """Overlap average + CFG combine (+ guidance rescale, Lin et al. 2305.08891 3.4) + one step of the linear update that carries DDIM with eta > 0 and
+    DPM-Solver++ 2M: coefficients = (sa_t, sb_t, k_x, k_0, k_1, k_v, k_z) of mmgt_amd.scheduler `update_coefficients`.  -> [new latents, x0]
+    (include/mmgt_hip.h: mmgt_sampler_step, mmgt_cfg_moments)."""
+    if len(coefficients) != 7:
+        raise RuntimeError(f"mmgt_hip::sampler_step: seven coefficients (sa_t, sb_t, k_x, k_0, k_1, k_v, k_z), got {len(coefficients)}")
+    x0 = torch.empty_like(latents)
+    return [hip.sampler_step(pred_sum, counter, latents, guidance, *coefficients, rescale=rescale, prev_x0=prev_x0, noise=noise, x0_out=x0), x0]
+
+
+@sampler_step.register_fake
+def _(pred_sum, counter, latents, prev_x0, noise, guidance, rescale, coefficients):
+    return [torch.empty_like(latents), torch.empty_like(latents)]
+
+
 OPS = ("gemm", "conv3x3_nhwc", "attention", "groupnorm_silu", "layernorm", "cfg_ddim_step", "attn_bank_fwd", "temporal_attn", "mmhaa_cross",
-       "ff_fused", "rowgemm320", "temporal_leg", "gn_silu_conv3x3", "vae_decode")
+       "ff_fused", "rowgemm320", "temporal_leg", "gn_silu_conv3x3", "vae_decode", "sampler_step")

@@ -75,6 +75,11 @@ def parse_args():
                    help="(n_slices, 80, 35) .npy of the reference's librosa baseline features for columns 1024:1059 (librosa is not part of "
                         "this build; without it those columns keep the hash-seeded stand-in)")
     p.add_argument("--save_cond", type=str, default=None, help="write the (n_slices, 80, 1059) SMGA conditioning handed to the sampler to this .npy")
+    p.add_argument("--sampler", default="ddim", choices=["ddim", "dpmpp2m"],
+                   help="the update rule: the reference's DDIM, or DPM-Solver++ 2M (second order, the same one UNet forward per step; meant for fewer --steps)")
+    p.add_argument("--eta", type=float, default=0.0, help="DDIM's stochasticity (0 = deterministic, 1 = ancestral); not with --sampler dpmpp2m")
+    p.add_argument("--guidance_rescale", type=float, default=0.0,
+                   help="in [0, 1]: rescale the guided prediction to the conditional one's standard deviation (Lin et al. 2305.08891, 3.4)")
     return p.parse_args()
 
 
@@ -155,6 +160,8 @@ def main():
     smga_sd = {k: (synth_tensor("smga." + k, s) if not k.endswith("rotary.freqs") else torch.zeros(s)) for k, s in keys.items()}
     audio2pose = SMGA(feature_type=a.feature_type, device=dev, dtype=dtype, state_dict=smga_sd)             # :198-200
     pipe = build_synthetic_pipeline(dev, dtype)
+    from mmgt_amd.scheduler import with_sampler
+    pipe.scheduler = with_sampler(pipe.scheduler, a.sampler)
     audioproj = AudioProjModel(seq_len=5, blocks=12, channels=768, intermediate_dim=512, output_dim=768, context_tokens=32,
                                device=dev, dtype=dtype)                                                     # :264-273
     audioproj.load_state_dict(synth_state_dict(audioproj.spec, prefix="audioproj.", device=dev))
@@ -244,7 +251,7 @@ def main():
     t0 = time.time()
     out = pipe(ref_img, pose, audio_tensor.float(), full, face, lips, a.W, a.H, a.L, a.steps, a.cfg,
                generator=torch.manual_seed(a.seed), motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c,
-               context_batch_size=a.context_batch_size, output_type="uint8")
+               context_batch_size=a.context_batch_size, output_type="uint8", eta=a.eta, guidance_rescale=a.guidance_rescale)
     torch.cuda.synchronize()
     timing["stage2_s"] = round(time.time() - t0, 3)
     v = torch.as_tensor(out.videos)                                                                          # (1, L, H, W, 3) uint8
@@ -267,7 +274,8 @@ def main():
         if lossy is not None:
             extra["webp_quality"] = lossy
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
-                      "dtype": a.dtype, "context_batch_size": a.context_batch_size, "keypoints_finite": bool(np.isfinite(kps).all()),
+                      "dtype": a.dtype, "context_batch_size": a.context_batch_size, "sampler": a.sampler, "eta": a.eta,
+                      "guidance_rescale": a.guidance_rescale, "keypoints_finite": bool(np.isfinite(kps).all()),
                       "mask_levels": [list(m.shape) for m in face], **timing, **extra}))
 
 

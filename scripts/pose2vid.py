@@ -3,6 +3,7 @@
 
     python scripts/pose2vid.py --synthetic -W 512 -H 512 -L 24 --steps 25         # BASELINE config 2 geometry
     python scripts/pose2vid.py --synthetic -W 64 -H 64 -L 8 --steps 4             # config 1 geometry
+    python scripts/pose2vid.py --synthetic --sampler dpmpp2m --steps 12 --guidance_rescale 0.7    # DPM-Solver++ 2M; --eta with ddim
 
     python scripts/pose2vid.py --image_path ref.png --pose_path pose_frames/ --face_mask_path face.npy --lips_mask_path lips.npy \
         [--hands_mask_path hands/] -c configs/prompts/animation.yaml          # the reference's single-sample mode (:196-300)
@@ -28,6 +29,8 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from mmgt_amd.scheduler import with_sampler  # noqa: E402
 
 
 def parse_args():
@@ -78,6 +81,11 @@ def parse_args():
     p.add_argument("--window-parallel", action="store_true",
                    help="one long video over all ranks of a torch.distributed.run launch: the windows of every DDIM step are "
                         "dealt to the ranks, one RCCL all-gather per round (SURVEY 8e, config 5)")
+    p.add_argument("--sampler", default="ddim", choices=["ddim", "dpmpp2m"],
+                   help="the update rule: the reference's DDIM, or DPM-Solver++ 2M (second order, the same one UNet forward per step; meant for fewer --steps)")
+    p.add_argument("--eta", type=float, default=0.0, help="DDIM's stochasticity (0 = deterministic, 1 = ancestral); not with --sampler dpmpp2m")
+    p.add_argument("--guidance_rescale", type=float, default=0.0,
+                   help="in [0, 1]: rescale the guided prediction to the conditional one's standard deviation (Lin et al. 2305.08891, 3.4)")
     return p.parse_args()
 
 
@@ -210,6 +218,7 @@ def run_files(a, dev, dtype):
             raise SystemExit(f"pose2vid: --{name} is required without --synthetic")
     t0 = time.time()
     pipe = build_synthetic(dev, dtype) if a.random_weights else build_from_checkpoints(a.config, a.num_c, dev, dtype)
+    pipe.scheduler = with_sampler(pipe.scheduler, a.sampler)
     t_build = time.time() - t0
     ref_img = load_ref_image(a, dev)
     pose, full, face, lips, L = load_inputs(a, dev)
@@ -219,7 +228,7 @@ def run_files(a, dev, dtype):
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, L, a.steps, a.cfg, generator=gen, motion_scale=[1.0, 1.0, 2.0],
                context_frames=a.num_c, context_batch_size=a.context_batch_size, output_type="jpeg" if a.format == "avi" else "uint8",
-               jpeg_quality=a.quality)
+               jpeg_quality=a.quality, eta=a.eta, guidance_rescale=a.guidance_rescale)
     torch.cuda.synchronize()
     dt = time.time() - t0
     save_dir = os.path.join(a.out_dir, f"multi_person_{a.num_c}")
@@ -242,7 +251,8 @@ def run_files(a, dev, dtype):
         shape = list(torch.as_tensor(out.videos).shape)
     print(json.dumps({"video": shape, "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype,
-                      "context_batch_size": a.context_batch_size, **extra}))
+                      "context_batch_size": a.context_batch_size, "sampler": a.sampler, "eta": a.eta, "guidance_rescale": a.guidance_rescale,
+                      **extra}))
 
 
 def main():
@@ -266,6 +276,7 @@ def main():
     t0 = time.time()
     # window-parallel: the same hash-seeded weights are built on every rank; clip-parallel: rank 0 broadcasts them
     pipe = build_synthetic_broadcast(dev, dtype, rank) if a.clip_parallel else build_synthetic(dev, dtype)
+    pipe.scheduler = with_sampler(pipe.scheduler, a.sampler)
     t_build = time.time() - t0
     lat = a.H // 8
     clip_id = rank if a.clip_parallel else 0                  # clip-parallel: rank r samples its own clip
@@ -292,7 +303,7 @@ def main():
                motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c, context_batch_size=a.context_batch_size,
                output_type="uint8" if a.clip_parallel else "tensor",
                decode=not a.no_decode,                         # CLIP embedding and ref_image_latents: HIP encoders, from ref_img
-               window_group=True if a.window_parallel else None)
+               window_group=True if a.window_parallel else None, eta=a.eta, guidance_rescale=a.guidance_rescale)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if a.clip_parallel:
@@ -339,6 +350,7 @@ def main():
     print(json.dumps({"video": list(v.shape), "saved": path, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "windows_per_step": len(list(__import__("mmgt_amd.context", fromlist=["uniform"]).uniform(
                           0, a.steps, a.L, a.num_c, 1, 4))), "context_batch_size": a.context_batch_size, "dtype": a.dtype,
+                      "sampler": a.sampler, "eta": a.eta, "guidance_rescale": a.guidance_rescale,
                       "finite": bool(torch.as_tensor(v).isfinite().all()), **extra}))
 
 
