@@ -33,6 +33,9 @@ class UNet2DConditionModel(UNet3DConditionModel):
         if not sample.is_cuda:
             raise RuntimeError("mmgt_amd.UNet2DConditionModel runs on the GPU only (no CPU path exists)")
         b, _, hh, ww = sample.shape
+        if hh % 8 or ww % 8:
+            # three stride-2 convs down and three 2x up-samplings back: any other side leaves the skip tensors one pixel apart
+            raise RuntimeError("latent height/width must be multiples of 8 (unet_2d_condition.py:872-1308: three down / up-sampling levels)")
         lpb = self.config.layers_per_block
         temb = self._time_embedding(timestep, b)
         x = hip.ncfhw_to_nhwc(sample.to(torch.float32)[:, :, None].contiguous(), 64, self._dtype)   # f = 1

@@ -69,6 +69,7 @@ def entry_specs():
     from mmgt_amd.side_models import pose_guider_spec
     from mmgt_amd.unet3d_spec import unet2d_reference_spec
     from mmgt_amd.vae import vae_decoder_spec
+    from tests import geometry_cases as gx
     from tests import golden_cases as gc
     from tests import test_pipeline_gpu as TP
     from tests import test_smga as TS
@@ -84,6 +85,10 @@ def entry_specs():
         "smga_sampler_bf16_floor": ("", (TS.smga_bf16_floor,)),
         "unet_512x512_twelve_frames": (repr(sorted(TU.TWELVE_FRAME_CASE.items())), (TU._run_oracle,)),
         "vae_decode_512x512_frame": ("", (TV._sd, TV.oracle_full_resolution_frame, vae_decoder_spec)),
+        # 192 / 320 / 384 px (tests/geometry_cases.py): oracle output + the two scalars of its CPU-bf16 floor
+        **{"unet_" + n: (repr(sorted(c.items())), (TU._run_oracle, TU.oracle_with_bf16_floor)) for n, c in gx.UNET_GEOMETRY.items()},
+        "pipeline_320px": (repr(sorted(gx.PIPELINE_320.items())), pipe + (TP.oracle_pipeline_320px,)),
+        "vae_decode_320x192_frame": (repr(gx.VAE_RECT), (TV._sd, TV.oracle_rectangular_frame, vae_decoder_spec)),
     }
 
 

@@ -719,3 +719,48 @@ def test_bench_options_plain_run_by_default(monkeypatch):
         bench.parse_args()
     monkeypatch.setenv("OMP_NUM_THREADS", "3")
     assert 1 <= bench._usable_cores() <= 3
+
+
+# ------------------------------------------------------------------------------------------------ launch counts by geometry
+def test_expected_paths_reproduces_the_asserted_launch_counts():
+    """tests/geometry_cases.expected_paths against the launch counts the 8 x 8 and 64 x 64 tests of tests/test_unet_gpu.py assert on the
+    device: nothing fused by geometry at (8, 8); 20 fused resnet legs and 15 epilogue tables at (64, 6); 10 fused temporal legs at (64, 12)
+    -- and none of them in fp32 mode."""
+    from tests import geometry_cases as gx
+    bf16 = torch.bfloat16
+    p = gx.expected_paths(8, 8, bf16)
+    assert set(p) == set(gx.PATHS)
+    assert p["mmgt_temporal_leg320"] == p["mmgt_gn_silu_conv3x3_unet"] == p["mmgt_gn_stats_finalize_unet"] == p["mmgt_conv_taps_gather"] == 0
+    assert (p["mmgt_rowgemm320"], p["mmgt_ff_fused"], p["mmgt_ff_fused_po"], p["mmgt_conv1x1_cat_nhwc"]) == (3, 1, 12, 29)
+    p = gx.expected_paths(64, 6, bf16)
+    assert (p["mmgt_gn_silu_conv3x3_unet"], p["mmgt_gn_stats_finalize_unet"], p["mmgt_temporal_leg320"]) == (20, 15, 0)
+    assert (p["mmgt_rowgemm320"], p["mmgt_conv_taps_gather"]) == (34, 1)
+    p = gx.expected_paths(64, 12, bf16)
+    assert (p["mmgt_temporal_leg320"], p["mmgt_gn_silu_conv3x3_unet"], p["mmgt_rowgemm320"]) == (10, 20, 24)
+    assert not any(gx.expected_paths(64, 12, torch.float32).values())
+    # the three new cases: what each is there to reach
+    assert gx.expected_paths(48, 12, bf16)["mmgt_gn_silu_conv3x3_unet"] == 10 and gx.expected_paths(48, 12, bf16)["mmgt_temporal_leg320"] == 10
+    p = gx.expected_paths(24, 24, bf16)
+    assert (p["mmgt_temporal_leg320"], p["mmgt_gn_silu_conv3x3_unet"], p["mmgt_rowgemm320"], p["mmgt_conv_taps_gather"]) == (10, 0, 3, 0)
+    p = gx.expected_paths(40, 5, bf16)
+    assert (p["mmgt_temporal_leg320"], p["mmgt_gn_silu_conv3x3_unet"], p["mmgt_rowgemm320"], p["mmgt_conv1x1_cat_nhwc"]) == (0, 0, 3, 32)
+
+
+def test_expected_paths_gates_agree_with_the_bindings():
+    """The geometry gates restated in tests/geometry_cases.py against the `*_supported` predicates of mmgt_amd/hip.py that are pure functions
+    of the shape, over every latent side the UNet accepts up to 64."""
+    from mmgt_amd import hip
+    from tests import geometry_cases as gx
+    bf16 = torch.bfloat16
+    for latent in range(8, 65, 8):
+        for frames in (5, 12, 24):
+            p = gx.expected_paths(latent, frames, bf16)
+            assert (p["mmgt_temporal_leg320"] == 10) == hip.temporal_leg320_supported(bf16, 320, 8, frames, latent * latent, 2)
+            legs = 2 * sum(n for l, c, n in ((0, 320, 5), (2, 1280, 5), (3, 1280, 7))
+                           if hip.gn_silu_conv3x3_unet_supported(bf16, c, 0, c, latent >> l, latent >> l))
+            assert p["mmgt_gn_silu_conv3x3_unet"] == legs
+        assert gx.refnet_fused_levels(latent) == tuple(l for l in (0, 2, 3) if hip.gn_silu_conv3x3_unet_supported(bf16, 1280, 0, 1280, latent >> l, latent >> l))
+    for h, w in ((40, 24), (64, 64), (8, 8), (2, 2), (6, 4)):
+        on = lambda s, cin, cout: hip.gn_silu_conv3x3_supported(bf16, cin, cout, h * s, w * s) and h * s * w * s > 256
+        assert gx.vae_gnconv_launches(h, w) == (10 if on(4, 256, 256) else 0) + (7 if on(8, 128, 128) else 0)
+    assert gx.vae_gnconv_launches(*gx.VAE_RECT) == 17 and not hip.gn_silu_conv3x3_supported(bf16, 256, 256, *gx.VAE_RECT)

@@ -168,6 +168,21 @@ def test_unet_full_width_config1_matches_reference(golden_dir):
     torch.testing.assert_close(out, g["script"], **TOL)
 
 
+def test_unet_full_width_lat40_matches_reference(golden_dir):
+    """The reference's own UNet at a 40 x 40 latent, 2 frames, script mode (sides 40 / 20 / 10 / 5: odd under the stride-2 convs and the
+    2x up-sampling; tools/refgen/gen_golden.py --only geometry): the oracle is a valid reference at the sizes of tests/geometry_cases.py."""
+    from tests import geometry_cases as gx
+    g = _load(golden_dir, "unet3d_full_lat40")
+    case = gx.GOLDEN_LAT40
+    sd = synth_state_dict(unet_spec(R.UNet3DConfig()))
+    inp = gc.unet_inputs(case)
+    with torch.no_grad():
+        out = R.unet3d_forward(sd, R.UNet3DConfig(), inp["sample"], inp["timestep"], inp["ehs"], inp["audio"], inp["pose"], inp["full"],
+                               inp["face"], inp["lips"], inp["motion_scale"], inp["banks"], weighted=True)
+    assert out.shape == g["script"].shape == (2, 4, case["frames"], case["latent"], case["latent"])
+    torch.testing.assert_close(out, g["script"], **TOL)
+
+
 # ----------------------------------------------------------------------------------------------- side models (G6)
 
 def test_pose_guider_and_audio_proj(golden_dir):

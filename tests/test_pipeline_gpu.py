@@ -78,6 +78,23 @@ def oracle_long_video(sds_cpu):
     return {"traj": traj}
 
 
+def oracle_pipeline_320px(sds_cpu):
+    """Latent trajectory of the fp32 oracle pipeline at 320 x 320 px x 5 frames, 2 DDIM steps, and the two scalars of its CPU-bf16 floor on
+    the final latents (max and mean of |denoiser under CPU bf16 - fp32|), for the two tests at that size."""
+    from oracle import pipeline_ref
+    from tests import geometry_cases as gx
+    inp = _inputs(gx.PIPELINE_320["frames"], gx.PIPELINE_320["latent"])
+    kw = dict(clip_image_embeds=inp["clip"], ref_image_latents=inp["ref_lat"], pose_images=inp["pose"], audio_tensor=inp["audio"],
+              full_mask=inp["full"], face_mask=inp["face"], lip_mask=inp["lips"], latents=inp["latents"],
+              num_inference_steps=gx.PIPELINE_320["steps"], guidance_scale=3.5, motion_scale=[1.0, 1.0, 2.0], decode=False)
+    traj = []
+    with torch.no_grad():
+        want = pipeline_ref.pose2vid(sds_cpu["unet"], sds_cpu["refnet"], sds_cpu["pose"], sds_cpu["vae"], trajectory=traj, **kw)
+        floor = (pipeline_ref.pose2vid(sds_cpu["unet"], sds_cpu["refnet"], sds_cpu["pose"], sds_cpu["vae"],
+                                       unet_dtype=torch.bfloat16, **kw) - want).abs()
+    return {"traj": traj, "floor_max": floor.max(), "floor_mean": floor.mean()}
+
+
 def _build(sds, dtype):
     from mmgt_amd.pipeline import Pose2VideoPipeline
     from mmgt_amd.reference_unet import UNet2DConditionModel
@@ -134,6 +151,45 @@ def test_pipeline_bf16_within_measured_noise_floor(weights):
           f"{floor.max().item():.3e} mean {floor.mean().item():.3e}; mean|x| {want.abs().mean().item():.3f}")
     assert torch.isfinite(got).all()
     assert d.max() <= 1.5 * floor.max() and d.mean() <= 1.5 * floor.mean()
+
+
+def _run_320px(sds, dtype, callback=None):
+    from tests import geometry_cases as gx
+    g = gx.PIPELINE_320
+    inp = _inputs(g["frames"], g["latent"])
+    pipe = _build(sds, dtype)
+    return pipe(None, inp["pose"], inp["audio"], inp["full"], inp["face"], inp["lips"], 8 * g["latent"], 8 * g["latent"], g["frames"],
+                g["steps"], 3.5, motion_scale=[1.0, 1.0, 2.0], latents=inp["latents"], clip_image_embeds=inp["clip"],
+                ref_image_latents=inp["ref_lat"], decode=False, callback=callback).videos.cpu()
+
+
+def test_pipeline_320px_fp32_matches_oracle(weights):
+    """320 x 320 px x 5 frames, 2 DDIM steps, fp32 mode: the PoseGuider's stride-2 chain from 320 x 320 pixels, the ReferenceNet hand-off at
+    1600 / 400 / 100 / 25 bank keys, one 5-frame window through the accumulate + CFG + DDIM step at 40 x 40 -- the latent trajectory of
+    every step against the oracle pipeline at the north-star tolerance."""
+    from tests import geometry_cases as gx
+    sds, sds_cpu = weights
+    traj = cached("pipeline_320px", lambda: oracle_pipeline_320px(sds_cpu))["traj"]
+    got = []
+    out = _run_320px(sds, torch.float32, callback=lambda i, t, lat: got.append(lat.cpu().clone()))
+    assert len(got) == len(traj) == gx.PIPELINE_320["steps"]
+    for i, (a, b) in enumerate(zip(got, traj)):
+        print(f"320 px fp32 pipeline, step {i}: max|d| {(a - b).abs().max().item():.3e} mean|x| {b.abs().mean().item():.3f}")
+        torch.testing.assert_close(a, b, rtol=1e-3, atol=1e-4)
+    torch.testing.assert_close(out, traj[-1], rtol=1e-3, atol=1e-4)
+
+
+def test_pipeline_320px_bf16_within_measured_noise_floor(weights):
+    """The same run in bf16 product mode: final latents within 1.5x the error of the oracle pipeline with its denoiser under CPU bf16."""
+    sds, sds_cpu = weights
+    ref = cached("pipeline_320px", lambda: oracle_pipeline_320px(sds_cpu))
+    want, fmax, fmean = ref["traj"][-1], ref["floor_max"].item(), ref["floor_mean"].item()
+    got = _run_320px(sds, torch.bfloat16)
+    d = (got - want).abs()
+    print(f"320 px bf16 pipeline final latents: HIP max|d| {d.max().item():.3e} mean|d| {d.mean().item():.3e}; CPU-bf16 floor max "
+          f"{fmax:.3e} mean {fmean:.3e}; mean|x| {want.abs().mean().item():.3f}")
+    assert torch.isfinite(got).all()
+    assert d.max() <= 1.5 * fmax and d.mean() <= 1.5 * fmean
 
 
 def test_long_video_96_frames_six_wrapping_windows(weights):

@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from mmgt_amd.synthetic import synth_state_dict  # noqa: E402
 from oracle import unet3d_ref as R  # noqa: E402
+from tests import geometry_cases as gx  # noqa: E402
 from tests import golden_cases as gc  # noqa: E402
 
 F32 = dict(rtol=1e-3, atol=1e-4)
@@ -41,6 +42,84 @@ def test_reference_net_banks(golden_dir, dtype):
             assert d.max().item() <= 1.2e-1 and d.mean().item() <= 1.2e-2, \
                 f"bank {k}: max|d| {d.max().item():.3e} mean|d| {d.mean().item():.3e}"
     torch.testing.assert_close(out.float().cpu(), g["sample"], **(F32 if dtype == torch.float32 else dict(rtol=0, atol=1e-1)))
+
+
+@pytest.fixture(scope="module")
+def refnet_sd():
+    from mmgt_amd.unet3d_spec import unet2d_reference_spec
+    sd = synth_state_dict(unet2d_reference_spec(), prefix="refnet.", device="cuda:0")
+    return sd, {k: v.cpu() for k, v in sd.items()}
+
+
+_GEOMETRY_ORACLE = {}
+
+
+def _refnet_geometry_oracle(sd_cpu, latent):
+    """({bank: fp32 oracle}, {bank: (max, mean) of |oracle under CPU bf16 - fp32 oracle|}) at a latent x latent reference image; computed once
+    per size and shared by the two dtypes (13-50 MB of banks: not a cache entry)."""
+    if latent not in _GEOMETRY_ORACLE:
+        inp = gc.refnet_inputs(dict(gc.REFNET_CASES["full"], latent=latent))
+        lo = lambda t: t.bfloat16() if t.is_floating_point() else t
+        with torch.no_grad():
+            ref, _ = R.reference_net_banks(sd_cpu, R.UNet3DConfig(), inp["latents"], inp["timestep"], inp["ehs"])
+            low, _ = R.reference_net_banks({k: lo(v) for k, v in sd_cpu.items()}, R.UNet3DConfig(), lo(inp["latents"]), inp["timestep"], lo(inp["ehs"]))
+        floors = {k: ((low[k].float() - v).abs().max().item(), (low[k].float() - v).abs().mean().item()) for k, v in ref.items()}
+        _GEOMETRY_ORACLE[latent] = (ref, floors)
+    return _GEOMETRY_ORACLE[latent]
+
+
+def _level_blocks(levels):
+    """Block prefixes of the resnets at UNet levels `levels` (level l: side latent / 2^l)."""
+    at = {0: ("down_blocks.0.", "up_blocks.3."), 1: ("down_blocks.1.", "up_blocks.2."), 2: ("down_blocks.2.", "up_blocks.1."),
+          3: ("down_blocks.3.", "mid_block.", "up_blocks.0.")}
+    return tuple(p for l in levels for p in at[l])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("latent", gx.REFNET_LATENTS)
+def test_reference_net_banks_at_320_and_384_px(refnet_sd, latent, dtype):
+    """`write_banks` at 40 x 40 and 48 x 48 reference latents (1600 / 400 / 100 / 25 and 2304 / 576 / 144 / 36 tokens per bank) against the
+    oracle on the same inputs: fp32 mode at the parity tolerance with the banks in the oracle's key order, bf16 mode per bank within 1.5x
+    the oracle's own CPU-bf16 error; the fused resnet legs that ran are exactly those of the levels whose sides tile into 16 x 16."""
+    from mmgt_amd.reference_unet import UNet2DConditionModel
+    sd, sd_cpu = refnet_sd
+    ref, floors = _refnet_geometry_oracle(sd_cpu, latent)
+    m = UNet2DConditionModel(device="cuda:0", dtype=dtype)
+    m.load_state_dict(sd)
+    inp = gc.refnet_inputs(dict(gc.REFNET_CASES["full"], latent=latent))
+    bank = m.write_banks(inp["latents"].cuda(), inp["timestep"], inp["ehs"].cuda())
+    assert list(bank) == list(ref) and len(bank) == 16
+    for k, v in bank.items():
+        d = (v.cpu() - ref[k]).abs()
+        fmax, fmean = floors[k]
+        print(f"latent {latent} {dtype} bank {k} {tuple(v.shape)}: max|d| {d.max().item():.3e} mean|d| {d.mean().item():.3e} "
+              f"(CPU-bf16 floor {fmax:.3e} / {fmean:.3e})")
+    for k, v in bank.items():
+        assert v.shape == ref[k].shape and torch.isfinite(v).all()
+        if dtype == torch.float32:
+            torch.testing.assert_close(v.cpu(), ref[k], **F32)
+        else:
+            d = (v.cpu() - ref[k]).abs()
+            assert d.max().item() <= 1.5 * floors[k][0] and d.mean().item() <= 1.5 * floors[k][1], k
+    # images of the fused legs are built by the forward that runs them: level 0 alone at 48 (five resnets, two legs each), none at 40, none in fp32 mode
+    levels = gx.refnet_fused_levels(latent) if dtype == torch.bfloat16 else ()
+    assert levels == ((0,) if latent == 48 and dtype == torch.bfloat16 else ())
+    want = {r + cv + ".rimg" for r in m._resnets if r.startswith(_level_blocks(levels)) for cv in (".conv1", ".conv2")}
+    assert len(want) == 10 * len(levels) and {k for k in m.w if k.endswith(".rimg")} == want
+
+
+def test_reference_net_refuses_latent_side_20(refnet_sd):
+    """The ReferenceNet shares the UNet's three stride-2 levels: a side that is no multiple of 8 is refused by name before any launch."""
+    from mmgt_amd import hip
+    from mmgt_amd.reference_unet import UNet2DConditionModel
+    sd, _ = refnet_sd
+    m = UNet2DConditionModel(device="cuda:0", dtype=torch.bfloat16)
+    m.load_state_dict(sd)
+    inp = gc.refnet_inputs(dict(gc.REFNET_CASES["full"], latent=20))
+    before = dict(hip._calls)
+    with pytest.raises(RuntimeError, match="multiples of 8"):
+        m.write_banks(inp["latents"].cuda(), inp["timestep"], inp["ehs"].cuda())
+    assert dict(hip._calls) == before and not m.bank
 
 
 def test_reference_attention_control_handoff(golden_dir):

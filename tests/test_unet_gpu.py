@@ -7,6 +7,8 @@ weights, latents and conditioning.
     gated against the MEASURED bf16 noise floor: the oracle run under PyTorch CPU bf16 on the same inputs (inside the test
     at config-1 size; at 512x512 the floor is the committed tools/gen_bf16_floor.py measurement at the full shape).  The HIP
     bf16 max|d| and mean|d| must stay within 1.5x that floor.
+  * between those two sizes (48-, 24- and 40-wide latents, tests/geometry_cases.py) both modes again, the bf16 floor measured by the
+    oracle at each case, and the launches of a bf16 forward counted against the restated gates.
 """
 import os
 
@@ -20,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 from mmgt_amd.synthetic import synth_state_dict  # noqa: E402
 from oracle import unet3d_ref as R  # noqa: E402
+from tests import geometry_cases as gx  # noqa: E402
 from tests import golden_cases as gc  # noqa: E402
 
 
@@ -449,3 +452,90 @@ def test_mmhaa_merged_bias_term_keeps_fp32_accuracy_with_blurred_masks(full_sd):
           f"{naive.item():.2e})")
     assert err32 <= 2 ** -14 and naive >= 8 * err32
     assert err <= 2 ** -8 * 1.01                                                 # ... and the bf16 output adds its one rounding
+
+
+# ---------------------------------------------------------------------------------- 384 / 192 / 320 px: the gates between 8 x 8 and 64 x 64 latents
+
+def oracle_with_bf16_floor(sd_cpu, case):
+    """The fp32 oracle's prediction for `case` and the two scalars of its CPU-bf16 floor, max and mean of |oracle under bf16 - fp32 oracle|
+    (tests/golden/oracle_cache/unet_<case>.pt): the reference side measures the gate of the bf16 product mode, never the code under test."""
+    ref = _run_oracle(sd_cpu, case)
+    floor = (_run_oracle(sd_cpu, case, dtype=torch.bfloat16) - ref).abs()
+    return {"ref": ref, "floor_max": floor.max(), "floor_mean": floor.mean()}
+
+
+def _geometry_oracle(sd_cpu, name):
+    return cached("unet_" + name, lambda: oracle_with_bf16_floor(sd_cpu, gx.UNET_GEOMETRY[name]))
+
+
+def _geometry_model(sd_gpu, case, dtype):
+    from mmgt_amd.unet3d import UNet3DConditionModel
+    m = UNet3DConditionModel(device="cuda:0", dtype=dtype)
+    m.load_state_dict(sd_gpu)
+    m.enable_gradient_checkpointing()
+    inp = _to_dev(gc.unet_inputs(case))
+    m.set_banks(inp["banks"])
+
+    def run():
+        out = m(inp["sample"], inp["timestep"], encoder_hidden_states=inp["ehs"], audio_embedding=inp["audio"], pose_cond_fea=inp["pose"],
+                full_mask=inp["full"], face_mask=inp["face"], body_mask=inp["lips"], motion_scale=inp["motion_scale"], return_dict=False)[0]
+        torch.cuda.synchronize()
+        return out.float().cpu()
+    return m, run
+
+
+@pytest.mark.parametrize("name", list(gx.UNET_GEOMETRY))
+def test_unet_geometry_fp32_mode_matches_oracle(full_sd, name):
+    """fp32-I/O mode at the north-star tolerance at 48 x 48 x 12, 24 x 24 x 24 and 40 x 40 x 5 latents: odd sides under the stride-2 convs and
+    the 2x up-sampling (20 -> 10 -> 5, 12 -> 6 -> 3), 9 .. 2304 bank keys, windows of 5, 12 and 24 frames."""
+    sd_gpu, sd_cpu = full_sd
+    case = gx.UNET_GEOMETRY[name]
+    ref = _geometry_oracle(sd_cpu, name)["ref"]
+    out = _run_hip(sd_gpu, case, torch.float32)
+    assert out.shape == ref.shape == (2, 4, case["frames"], case["latent"], case["latent"])
+    print(f"{name} fp32 mode: max|d| {(out - ref).abs().max().item():.3e} mean|x| {ref.abs().mean().item():.3f}")
+    torch.testing.assert_close(out, ref, rtol=1e-3, atol=1e-4)
+
+
+@pytest.mark.parametrize("name", list(gx.UNET_GEOMETRY))
+def test_unet_geometry_bf16_mode_floor_paths_and_repeatability(full_sd, name):
+    """bf16 product mode at the same three geometries, default switches: the launches of one forward are those the restated gates predict
+    (tests/geometry_cases.expected_paths: which blocks ran fused is asserted, not assumed), the result is finite and within 1.5x the
+    CPU-bf16 floor of the oracle at this very case, and a second forward repeats the first bit for bit."""
+    from mmgt_amd import hip
+    sd_gpu, sd_cpu = full_sd
+    case = gx.UNET_GEOMETRY[name]
+    o = _geometry_oracle(sd_cpu, name)
+    ref, fmax, fmean = o["ref"], o["floor_max"].item(), o["floor_mean"].item()
+    m, run = _geometry_model(sd_gpu, case, torch.bfloat16)
+    before = {k: hip.call_count(k) for k in gx.PATHS}
+    out = run()
+    got = {k: hip.call_count(k) - before[k] for k in gx.PATHS}
+    d = (out - ref).abs()
+    print(f"{name} bf16 mode: max|d| {d.max().item():.3e} mean|d| {d.mean().item():.3e} (floor {fmax:.3e} / {fmean:.3e}); launches {got}")
+    assert got == gx.expected_paths(case["latent"], case["frames"], torch.bfloat16)
+    assert torch.isfinite(out).all()
+    assert d.max() <= FLOOR_SLACK * fmax and d.mean() <= FLOOR_SLACK * fmean
+    assert torch.equal(run(), out)
+
+
+def test_unet_matches_reference_golden_lat40(full_sd, golden_dir):
+    """Straight against the REFERENCE's own output at a 40 x 40 latent, 2 frames, script mode (tests/golden/unet3d_full_lat40.npz)."""
+    sd_gpu, _ = full_sd
+    g = torch.from_numpy(np.load(os.path.join(golden_dir, "unet3d_full_lat40.npz"))["script"])
+    out = _run_hip(sd_gpu, gx.GOLDEN_LAT40, torch.float32)
+    print("lat40 fp32 mode vs reference golden: max|d|", (out - g).abs().max().item())
+    torch.testing.assert_close(out, g, rtol=1e-3, atol=1e-4)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_unet_refuses_latent_side_20_before_any_launch(full_sd, dtype):
+    """A side that is no multiple of 8 cannot pass the three stride-2 convs and come back through the up-sampling (unet_3d.py:461-469): the
+    named error, and nothing has been launched when it is raised."""
+    from mmgt_amd import hip
+    sd_gpu, _ = full_sd
+    m, run = _geometry_model(sd_gpu, dict(gc.UNET_CASES["full_cfg1"], frames=2, latent=20), dtype)
+    before = dict(hip._calls)
+    with pytest.raises(RuntimeError, match="multiples of 8"):
+        run()
+    assert dict(hip._calls) == before

@@ -205,6 +205,51 @@ def test_hip_vae_full_resolution_frame():
     assert torch.equal(both, vae.decode_video(lat, frames_per_batch=2))                      # repeatable
 
 
+def oracle_rectangular_frame():
+    """The oracle's decode of one 40 x 24 latent (a 320 x 192 px frame) and the two scalars of its CPU-bf16 floor, max and mean of |decode with
+    bf16 weights and activations - fp32 decode|: tests/golden/oracle_cache/vae_decode_320x192_frame.pt."""
+    from tests import geometry_cases as gx
+    sd = _sd()
+    lat = hash_uniform("vae.lat_rect", (1, 4, 1) + gx.VAE_RECT, 1.0)
+    with torch.no_grad():
+        ref = vae_ref.decode_latents(sd, lat)
+        low = vae_ref.decode_latents({k: v.bfloat16() for k, v in sd.items()}, lat.bfloat16()).float()
+    floor = (low - ref).abs()
+    return {"ref": ref, "floor_max": floor.max(), "floor_mean": floor.mean()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_hip_vae_rectangular_frame_320x192(dtype):
+    """A 40 x 24 latent -> 320 x 192 px: rows and columns differ at every level, the mid-block attention has 960 tokens (no multiple of 256: the
+    fp32 kernels in both modes) and the fused GroupNorm -> SiLU -> conv legs are off at the 40 x 24 level's sides and on from 160 x 96 up.
+    fp32 mode at the file's parity tolerance; bf16 mode within 1.5x the CPU-bf16 floor of the same oracle, with the fused launches counted."""
+    from mmgt_amd import hip
+    from mmgt_amd.vae import AutoencoderKL
+    from tests import geometry_cases as gx
+    from tests.oracle_cache import cached
+    o = cached("vae_decode_320x192_frame", oracle_rectangular_frame)
+    ref, fmax, fmean = o["ref"], o["floor_max"].item(), o["floor_mean"].item()
+    h, w = gx.VAE_RECT
+    assert ref.shape == (1, 3, 1, 8 * h, 8 * w)
+    vae = AutoencoderKL(device="cuda:0", dtype=dtype)
+    vae.load_state_dict(_sd("cuda:0"))
+    lat = hash_uniform("vae.lat_rect", (1, 4, 1, h, w), 1.0).cuda()
+    n0 = hip.call_count("mmgt_gn_silu_conv3x3")
+    out = vae.decode_video(lat, frames_per_batch=1).cpu()
+    launches = hip.call_count("mmgt_gn_silu_conv3x3") - n0
+    d = (out - ref).abs()
+    print(f"320x192 VAE frame, {dtype}: max|d| {d.max().item():.3e} mean|d| {d.mean().item():.3e} (CPU-bf16 floor {fmax:.3e} / {fmean:.3e}); "
+          f"{launches} fused launches")
+    assert out.shape == ref.shape and torch.isfinite(out).all()
+    if dtype == torch.float32:
+        assert launches == 0
+        torch.testing.assert_close(out, ref, rtol=1e-3, atol=1e-4)
+    else:
+        assert launches == gx.vae_gnconv_launches(h, w) == 17
+        assert d.max() <= 1.5 * fmax and d.mean() <= 1.5 * fmean
+
+
 @pytest.mark.gpu
 def test_hip_vae_never_runs_the_unet_fused_leg():
     """csrc/rconv.hip cuts its output into blocks of 320 / 256 / 160 channels of a multiple of 160: the decoder's 512- and 256-wide convs are

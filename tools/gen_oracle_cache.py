@@ -58,6 +58,23 @@ def main():
         sd_cpu = synth_state_dict(unet3d_spec(), device="cpu")
         emit("unet_512x512_twelve_frames", lambda: TU._run_oracle(sd_cpu, TU.TWELVE_FRAME_CASE))
         del sd_cpu
+    from tests import geometry_cases as gx
+    if not only or only & {"unet_" + n for n in gx.UNET_GEOMETRY}:
+        from mmgt_amd.synthetic import synth_state_dict
+        from mmgt_amd.unet3d_spec import unet3d_spec
+        from tests import test_unet_gpu as TU
+        sd_cpu = synth_state_dict(unet3d_spec(), device="cpu")
+        for n, case in gx.UNET_GEOMETRY.items():
+            emit("unet_" + n, lambda: TU.oracle_with_bf16_floor(sd_cpu, case))
+        del sd_cpu
+    if want("pipeline_320px"):
+        from tests import test_pipeline_gpu as TP
+        sds_cpu = TP.build_weights("cpu")
+        emit("pipeline_320px", lambda: TP.oracle_pipeline_320px(sds_cpu))
+        del sds_cpu
+    if want("vae_decode_320x192_frame"):
+        from tests import test_vae as TV
+        emit("vae_decode_320x192_frame", TV.oracle_rectangular_frame)
     if want("vae_decode_512x512_frame"):
         from tests import test_vae as TV
         emit("vae_decode_512x512_frame", TV.oracle_full_resolution_frame)

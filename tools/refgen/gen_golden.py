@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools", "refgen"))
 import refload  # noqa: E402
 
 refload.setup()
+from tests import geometry_cases as gx  # noqa: E402
 from tests import golden_cases as gc  # noqa: E402
 from mmgt_amd.synthetic import synth_state_dict  # noqa: E402
 
@@ -42,8 +43,8 @@ def gen_context():
     save("context_windows", **out)
 
 
-def gen_unet(case_name):
-    case = gc.UNET_CASES[case_name]
+def gen_unet(case_name, case=None, modes=None):
+    case = case or gc.UNET_CASES[case_name]
     from src.models.attention import TemporalBasicTransformerBlock
     from src.models.mutual_self_attention import ReferenceAttentionControl
     t0 = time.time()
@@ -60,7 +61,7 @@ def gen_unet(case_name):
             key = name.replace(".transformer_blocks.0", "")
             mod.bank = [inp["banks"][key].to(torch.float16)]          # what update(writer) stores: mutual_self_attention.py:340
     outs = {}
-    for mode in (("script",) if case_name == "full_cfg2" else ("script", "eval")):
+    for mode in modes or (("script",) if case_name == "full_cfg2" else ("script", "eval")):
         if mode == "script":                                          # scripts/pose2vid.py:151-156,183-184
             m.train()
             m.enable_gradient_checkpointing()
@@ -210,11 +211,13 @@ if __name__ == "__main__":
     steps = {"context": gen_context, "interp": gen_interp, "side": gen_side_models, "blocks": gen_blocks,
              "refnet_tiny": lambda: gen_refnet("tiny"), "refnet_full": lambda: gen_refnet("full"),
              "tiny": lambda: gen_unet("tiny"), "full": lambda: gen_unet("full_cfg1"),
-             "full_cfg2": lambda: gen_unet("full_cfg2")}
+             "full_cfg2": lambda: gen_unet("full_cfg2"),
+             # 40 x 40 latent (320 px), 2 frames, full width, script mode: sides 40 / 20 / 10 / 5 (tests/geometry_cases.GOLDEN_LAT40)
+             "geometry": lambda: gen_unet("full_lat40", gx.GOLDEN_LAT40, ("script",))}
     for k, fn in steps.items():
         if a.only and k != a.only:
             continue
-        if k == "full_cfg2" and a.only != k:        # minutes of CPU and ~15 GB: only on request
+        if k in ("full_cfg2", "geometry") and a.only != k:        # minutes of CPU and ~15 GB (full_cfg2) / a second full-width model: only on request
             continue
         if k == "full" and a.skip_full:
             continue
