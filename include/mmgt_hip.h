@@ -606,6 +606,27 @@ int mmgt_webp_untransform(const long long* tab, unsigned int* scratch, long long
  * draws nothing. */
 int mmgt_webp_compose(const long long* tab, const unsigned int* argb, long long argb_words, unsigned int* carry, unsigned char* out, int n, int H, int W,
                       void* stream);
+/* ---- WebP lossy input path (csrc/vp8dec.hip, csrc/vp8dec_core.h, mmgt_amd/video_in.py): a set of n VP8 key frames.  Every buffer is a
+ * device pointer; the status words are those of csrc/vp8dec_core.h (0: fine).  tab (n, 8) long long is one row per frame (vp8dec_core.h: V8D_BEGIN
+ * .. V8D_H): the `VP8 ` payload's byte range in data, offset and count of its scratch words (v8d_frame_words(W, H) at least, the offset a
+ * multiple of 4), offset of its ARGB words, width and height (1 .. 16383).  A row that names bytes or words outside the buffers gives status 1 and
+ * touches nothing.  Arguments outside the stated range: non-zero, nothing launched, mmgt_last_error() says "range".
+ * parse: frame header, first partition (segments, filter, quantisers, probability updates, every macroblock's segment, skip flag and modes) and
+ * token partitions -> header block (64 words), 32 bytes and 384 int16 dequantised coefficients per macroblock; data_bytes a positive multiple of
+ * 16, scratch 16-byte aligned, 1 <= n <= 65535.  One 512-thread workgroup per frame; its loops run mbw * mbh rounds and
+ * ceil(mbh / partitions) * max(mbw, partitions) + partitions steps, whatever the stream says. */
+int mmgt_vp8dec_parse(const unsigned char* data, long long data_bytes, const long long* tab, unsigned int* scratch, long long scratch_words, int* status,
+                      int n, void* stream);
+/* reconstruct: prediction plus residual of every macroblock along the fronts x + 2 y -> the unfiltered Y, U, V planes (padded to whole
+ * macroblocks) behind the coefficients; a frame whose parse left no valid header block gives status 7 and writes nothing.  One 64-thread
+ * workgroup per frame, mbw + 2 (mbh - 1) fronts. */
+int mmgt_vp8dec_reconstruct(const long long* tab, unsigned int* scratch, long long scratch_words, int* status, int n, void* stream);
+/* filter: the simple or the normal loop filter in place, along the same fronts, in libwebp's order within a macroblock. */
+int mmgt_vp8dec_filter(const long long* tab, unsigned int* scratch, long long scratch_words, int* status, int n, void* stream);
+/* output: fancy upsampling and YUV -> RGB -> the ARGB words (alpha 255) of each frame's own rectangle, W * H of them at argb + tab[f].pix, as
+ * mmgt_webp_compose takes them.  max_pixels: the largest W * H among the rows (1 .. 16383 * 16383); one thread per pixel. */
+int mmgt_vp8dec_output(const long long* tab, unsigned int* scratch, long long scratch_words, unsigned int* argb, long long argb_words, int* status, int n,
+                       long long max_pixels, void* stream);
 /* SMGA key points -> the four frame streams of Stage 2, drawn on the device: kp (frames, 134, 3) fp32 = SMGA's normalised
  * (x, y, score) features.  Replaces data/extract_movment_mask_all.py:319-321 `pose_vid_generator` (denormalize :128-132, mask_leg :66-89,
  * process_keypoints :98-119), src/dwpose/__init__.py:220-283 `DWposeDetector_movment_mask.__call__` with draw_pose / draw_pose_mask_head /

@@ -152,6 +152,10 @@ _SIGS = {
     "mmgt_webp_decode": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
     "mmgt_webp_untransform": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
     "mmgt_webp_compose": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_vp8dec_parse": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
+    "mmgt_vp8dec_reconstruct": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
+    "mmgt_vp8dec_filter": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
+    "mmgt_vp8dec_output": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
@@ -1856,6 +1860,64 @@ def webp_compose(tab, argb, carry, H, W, out=None):
         raise RuntimeError(f"webp_compose: out must be contiguous uint8 ({n}, {H}, {W}, 3) on {argb.device}")
     _check(lib().mmgt_webp_compose(_ptr(tab), _ptr(argb), argb.numel(), _ptr(carry), _ptr(out), n, H, W, _stream()), "mmgt_webp_compose")
     return out
+
+
+# --------------------------------------------------------------------------------------------------------------- WebP lossy input (csrc/vp8dec.hip)
+
+VP8DEC_TAB = 8                      # long long words per frame row (csrc/vp8dec_core.h: V8D_TAB)
+
+
+def _vp8dec_tab(tab, what):
+    if tab.dtype != torch.int64 or tab.dim() != 2 or tab.shape[1] != VP8DEC_TAB or tab.shape[0] < 1 or not tab.is_contiguous():
+        raise RuntimeError(f"{what}: expected tab int64 (n, {VP8DEC_TAB}), n >= 1, contiguous")
+    return tab.shape[0]
+
+
+def vp8dec_parse(data, tab, scratch, out=None):
+    """The `VP8 ` payloads of n frames (data uint8, a multiple of 16 bytes; tab int64 (n, 8), one row per frame: include/mmgt_hip.h) -> every
+    frame's header block, macroblock modes and dequantised coefficients in scratch int32 (words,) at its row's offset, and status (n,) int32, which
+    is returned.  `out`: the status tensor to write into."""
+    _dev(data, tab, scratch)
+    n = _vp8dec_tab(tab, "vp8dec_parse")
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise RuntimeError("vp8dec_parse: expected data uint8 (bytes,), contiguous")
+    _webp_words(scratch, "scratch", "vp8dec_parse")
+    status = _status_words(out, n, data.device, "vp8dec_parse")
+    _check(lib().mmgt_vp8dec_parse(_ptr(data), data.numel(), _ptr(tab), _ptr(scratch), scratch.numel(), _ptr(status), n, _stream()), "mmgt_vp8dec_parse")
+    return status
+
+
+def vp8dec_reconstruct(tab, scratch, out=None):
+    """Every parsed frame's prediction plus residual -> its unfiltered planes in scratch; status (n,) int32 is returned."""
+    _dev(tab, scratch)
+    n = _vp8dec_tab(tab, "vp8dec_reconstruct")
+    _webp_words(scratch, "scratch", "vp8dec_reconstruct")
+    status = _status_words(out, n, scratch.device, "vp8dec_reconstruct")
+    _check(lib().mmgt_vp8dec_reconstruct(_ptr(tab), _ptr(scratch), scratch.numel(), _ptr(status), n, _stream()), "mmgt_vp8dec_reconstruct")
+    return status
+
+
+def vp8dec_filter(tab, scratch, out=None):
+    """Every reconstructed frame's loop filter, in place in scratch; status (n,) int32 is returned."""
+    _dev(tab, scratch)
+    n = _vp8dec_tab(tab, "vp8dec_filter")
+    _webp_words(scratch, "scratch", "vp8dec_filter")
+    status = _status_words(out, n, scratch.device, "vp8dec_filter")
+    _check(lib().mmgt_vp8dec_filter(_ptr(tab), _ptr(scratch), scratch.numel(), _ptr(status), n, _stream()), "mmgt_vp8dec_filter")
+    return status
+
+
+def vp8dec_output(tab, scratch, argb, max_pixels, out=None):
+    """Every frame's planes -> the ARGB words (alpha 255) of its rectangle in argb int32 (words,) at its row's offset, as webp_compose takes them;
+    max_pixels: the largest W * H among the rows.  status (n,) int32 is returned."""
+    _dev(tab, scratch, argb)
+    n = _vp8dec_tab(tab, "vp8dec_output")
+    _webp_words(scratch, "scratch", "vp8dec_output")
+    _webp_words(argb, "argb", "vp8dec_output")
+    status = _status_words(out, n, scratch.device, "vp8dec_output")
+    _check(lib().mmgt_vp8dec_output(_ptr(tab), _ptr(scratch), scratch.numel(), _ptr(argb), argb.numel(), _ptr(status), n, int(max_pixels), _stream()),
+           "mmgt_vp8dec_output")
+    return status
 
 
 def dwpose_draw(kp, H=512, W=512):

@@ -786,7 +786,8 @@ class WebpFrame:
     dispose: bool                                # ANMF flag bit 0: the rectangle is zeroed before the next frame draws
     alpha_is_used: bool                          # the VP8L header's bit
     key: bool                                    # libwebp's key frame: the canvas is zeroed before it draws, and it does not blend
-    payload: bytes                               # the VP8L chunk's body
+    payload: bytes                               # the VP8L chunk's body (of a lossy frame: the `VP8 ` chunk's, with its padding byte if it has one)
+    lossy: bool = False                          # a VP8 key frame (parse_webp(lossy=True) only)
 
 
 @dataclass
@@ -809,8 +810,35 @@ def _vp8l_header(payload, what):
     return (v >> 8 & 0x3FFF) + 1, (v >> 22 & 0x3FFF) + 1, bool(v >> 36 & 1)
 
 
-def parse_webp(data) -> WebpHeader:
-    """One lossless WebP file (bytes), still or animated -> WebpHeader.  ICCP, EXIF, XMP and unknown chunks are skipped, bytes behind the RIFF size
+def _vp8_header(payload, what):
+    """The 10-byte frame header of a `VP8 ` chunk -> (width, height); everything libwebp refuses there is refused here."""
+    if len(payload) < 10:
+        raise ValueError(f"parse_webp: the VP8 chunk of {what} holds {len(payload)} bytes: no room for its frame header")
+    tag = int.from_bytes(payload[:3], "little")
+    if tag & 1:
+        raise ValueError(f"parse_webp: the VP8 chunk of {what} is not a key frame (inter frames are not decoded)")
+    if tag >> 1 & 7 > 3:
+        raise ValueError(f"parse_webp: bad VP8 profile {tag >> 1 & 7} in {what} (0 .. 3)")
+    if not tag >> 4 & 1:
+        raise ValueError(f"parse_webp: the VP8 frame of {what} is not shown")
+    if payload[3:6] != b"\x9d\x01\x2a":
+        raise ValueError(f"parse_webp: bad VP8 start code {bytes(payload[3:6]).hex()} in {what} (9d012a)")
+    if (tag >> 5) > len(payload) - 10:
+        raise ValueError(f"parse_webp: the first partition of {what} ({tag >> 5} bytes) runs past its VP8 chunk ({len(payload) - 10} bytes behind "
+                         "the frame header)")
+    w, h = int.from_bytes(payload[6:8], "little") & 0x3FFF, int.from_bytes(payload[8:10], "little") & 0x3FFF
+    if not w or not h:
+        raise ValueError(f"parse_webp: the VP8 frame of {what} has an empty size ({w} x {h})")
+    return w, h
+
+
+def parse_webp(data, lossy=False) -> WebpHeader:
+    """One WebP file (bytes), still or animated -> WebpHeader.  With lossy=False (the default) only lossless files are taken, as described below;
+    with lossy=True a `VP8 ` chunk (a lossy key frame) is taken as a still and as the image of an ANMF frame, a file may mix `VP8 ` and
+    VP8L frames, and the further refusals are: an ALPH chunk (named as such), a VP8 payload that is not a shown key frame of profile 0 .. 3, a bad
+    start code, a first partition that runs past the chunk, a VP8 size that differs from the ANMF rectangle or the VP8X canvas.
+
+    lossy=False: one lossless WebP file (bytes), still or animated -> WebpHeader.  ICCP, EXIF, XMP and unknown chunks are skipped, bytes behind the RIFF size
     are ignored.  ValueError for everything outside the decoder's scope: not a RIFF/WEBP file, a RIFF size or a chunk that runs past the file, a
     lossy `VP8 ` or an ALPH chunk, a VP8L signature other than 0x2f or a version other than 0, a frame whose VP8L size differs from its ANMF size,
     a frame rectangle that leaves the canvas, a VP8X canvas that differs from a still's VP8L size, image data on the wrong side of the VP8X
@@ -829,13 +857,16 @@ def parse_webp(data) -> WebpHeader:
             kind, ln = data[pos:pos + 4], int.from_bytes(data[pos + 4:pos + 8], "little")
             if pos + 8 + ln > stop:
                 raise ValueError(f"parse_webp: chunk {kind!r} at byte {pos} runs past the end of {where}")
-            if kind in (b"VP8 ", b"ALPH"):
+            if kind in (b"VP8 ", b"ALPH") and not lossy:
                 raise ValueError(f"parse_webp: lossy WebP (VP8) is not decoded (chunk {kind!r} at byte {pos}; VP8L only)")
+            if kind == b"ALPH":
+                raise ValueError(f"parse_webp: an ALPH chunk (the alpha plane of a lossy frame) is not decoded (at byte {pos}); such a file goes "
+                                 "through the host route")
             yield kind, pos + 8, ln
             pos += 8 + ln + (ln & 1)
 
     u24 = lambda at: int.from_bytes(data[at:at + 3], "little")
-    canvas, flags, loop, stills, frames = None, 0, None, [], []
+    canvas, flags, loop, stills, frames, still_lossy = None, 0, None, [], [], False
     for kind, at, ln in chunks(12, end, "the file"):
         if kind == b"VP8X":
             if ln < 10 or canvas is not None or stills or frames:
@@ -845,37 +876,42 @@ def parse_webp(data) -> WebpHeader:
             if ln < 6 or canvas is None or frames:
                 raise ValueError("parse_webp: bad ANIM chunk (its length or place)")
             loop = int.from_bytes(data[at + 4:at + 6], "little")
-        elif kind == b"VP8L":
-            stills.append(data[at:at + ln])
+        elif kind == b"VP8L" or (lossy and kind == b"VP8 "):
+            still_lossy = kind == b"VP8 "
+            stills.append(data[at:min(at + ln + (ln & 1), end)] if still_lossy else data[at:at + ln])   # libwebp reads a VP8 chunk with its padding byte
         elif kind == b"ANMF":
             k = len(frames)
             if loop is None:
                 raise ValueError("parse_webp: an ANMF chunk before any ANIM chunk")
             if ln < 16:
                 raise ValueError(f"parse_webp: the ANMF chunk of frame {k} holds {ln} bytes: no room for its header")
-            payload = None
+            payload, frame_lossy = None, False
             for sub, sat, sln in chunks(at + 16, at + ln, f"the ANMF chunk of frame {k}"):
-                if sub == b"VP8L" and payload is None:
-                    payload = data[sat:sat + sln]
+                if (sub == b"VP8L" or (lossy and sub == b"VP8 ")) and payload is None:
+                    payload, frame_lossy = data[sat:sat + sln], sub == b"VP8 "
+                    if frame_lossy:                                           # libwebp reads a VP8 chunk with its padding byte
+                        payload = data[sat:min(sat + sln + (sln & 1), at + ln)]
             if payload is None:
-                raise ValueError(f"parse_webp: frame {k} has no VP8L chunk")
-            w, h, alpha = _vp8l_header(payload, f"frame {k}")
+                raise ValueError(f"parse_webp: frame {k} has no VP8L chunk" + (" and no VP8 chunk" if lossy else ""))
+            w, h, alpha = (*_vp8_header(payload, f"frame {k}"), False) if frame_lossy else _vp8l_header(payload, f"frame {k}")
             x, y, fw, fh = 2 * u24(at), 2 * u24(at + 3), u24(at + 6) + 1, u24(at + 9) + 1
             if (w, h) != (fw, fh):
-                raise ValueError(f"parse_webp: the VP8L size of frame {k} ({w} x {h}) differs from its ANMF size ({fw} x {fh})")
-            frames.append(WebpFrame(x, y, w, h, u24(at + 12), not data[at + 15] & 2, bool(data[at + 15] & 1), alpha, False, payload))
+                raise ValueError(f"parse_webp: the {'VP8' if frame_lossy else 'VP8L'} size of frame {k} ({w} x {h}) differs from its ANMF size "
+                                 f"({fw} x {fh})")
+            frames.append(WebpFrame(x, y, w, h, u24(at + 12), not data[at + 15] & 2, bool(data[at + 15] & 1), alpha, False, payload, frame_lossy))
         # ICCP, EXIF, XMP and unknown chunks: skipped
     animated = bool(flags & 2)
     if (frames and not animated) or (stills and animated):
         raise ValueError("parse_webp: image data on the wrong side of the VP8X animation flag (ANMF without it, or VP8L beside it)")
     if len(stills) > 1:
-        raise ValueError("parse_webp: more than one VP8L chunk in a still")
+        raise ValueError("parse_webp: more than one VP8L chunk in a still" if not lossy else "parse_webp: more than one image chunk in a still")
     if stills:
-        w, h, alpha = _vp8l_header(stills[0], "the still")
+        w, h, alpha = (*_vp8_header(stills[0], "the still"), False) if still_lossy else _vp8l_header(stills[0], "the still")
         if canvas is not None and canvas != (w, h):
-            raise ValueError(f"parse_webp: the VP8X canvas ({canvas[0]} x {canvas[1]}) differs from the still's VP8L size ({w} x {h})")
+            raise ValueError(f"parse_webp: the VP8X canvas ({canvas[0]} x {canvas[1]}) differs from the still's {'VP8' if still_lossy else 'VP8L'} "
+                             f"size ({w} x {h})")
         canvas = (w, h)
-        frames = [WebpFrame(0, 0, w, h, 0, False, False, alpha, True, stills[0])]
+        frames = [WebpFrame(0, 0, w, h, 0, False, False, alpha, True, stills[0], still_lossy)]
     if not frames:
         raise ValueError("parse_webp: no frames")
     W, H = canvas
@@ -941,8 +977,13 @@ def webp_operands(headers, limit: Optional[int] = None, scratch_bytes: Optional[
     return tab, data, chunks
 
 
-def decode_webp_frames(files, device="cuda", out=None, limit=None):
-    """Lossless WebP files (a list of bytes; one bytes object is a list of one), still or animated, all of one canvas size -> (n, H, W, 3) uint8
+def decode_webp_frames(files, device="cuda", out=None, limit=None, lossy=False):
+    """lossy=True: as below, and lossy frames (`VP8 ` chunks: key frames of any profile, partition count, segment, filter and mode use)
+    are decoded too, alone or mixed with VP8L frames in one file or one call; byte for byte PIL's frames again.  What parse_webp(lossy=True)
+    refuses (ALPH, inter frames, a bad frame header) is a ValueError before any launch; a VP8 stream that does not decode is a RuntimeError naming
+    the frame and the cause (VP8_STATUS_TEXT).  lossy=False (the default) is the lossless decoder unchanged:
+
+    Lossless WebP files (a list of bytes; one bytes object is a list of one), still or animated, all of one canvas size -> (n, H, W, 3) uint8
     RGB on `device`, contiguous, n = all frames of all files in order (the first `limit` of them; later ones are neither decoded nor composed):
     byte for byte what PIL's ImageSequence.Iterator(Image.open(f)) gives after convert("RGB") -- the whole of VP8L, and sub-rectangles, blend and
     dispose composed as libwebp's WebPAnimDecoder composes them, anew at each file.  `out`: a tensor of that shape to write into.  Out-of-scope
@@ -951,6 +992,8 @@ def decode_webp_frames(files, device="cuda", out=None, limit=None):
     allowance holds (WEBPDEC_GROUP_BYTES) says so in its status, and the call's launches are then run once more with what such frames need."""
     if isinstance(files, (bytes, bytearray, memoryview)):
         files = [files]
+    if lossy:
+        return _decode_webp_headers_lossy([parse_webp(b, lossy=True) for b in files], device, out, limit)
     headers = [parse_webp(b) for b in files]
     return _decode_webp_headers(headers, device, out, limit)
 
@@ -991,12 +1034,138 @@ def _decode_webp_headers(headers, device, out=None, limit=None, caps=None):
     return out
 
 
-def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
+# ------------------------------------------------------------------------------------------------------------------ WebP lossy
+
+# csrc/vp8dec_core.h's status words
+VP8_STATUS_TEXT = {1: "a frame descriptor outside the batch", 2: "a frame header that is no shown key frame of profile 0 .. 3 and the frame's size",
+                   3: "a first partition that runs past the payload", 4: "a partition table that runs past the payload, or an empty last partition",
+                   5: "a first partition that ends inside the header or the macroblock modes",
+                   6: "a token partition that ends inside its macroblocks", 7: "no parsed frame to reconstruct, filter or convert"}
+
+# csrc/vp8dec_core.h's table row (checked against the binding's VP8DEC_TAB on every call)
+_V8D_BEGIN, _V8D_END, _V8D_SCR, _V8D_CAP, _V8D_PIX, _V8D_W, _V8D_H = range(7)
+VP8_TAB = 8
+_V8D_HDR_WORDS, _V8D_MB_BYTES = 64, 32 + 384 * 2 + 384
+
+
+def vp8_frame_scratch_words(f: WebpFrame) -> int:
+    """Scratch words of one lossy frame: the header block and, per macroblock, its modes (32 bytes), 384 int16 coefficients and 384 plane bytes."""
+    return _V8D_HDR_WORDS + -(-f.width // 16) * -(-f.height // 16) * _V8D_MB_BYTES // 4
+
+
+def webp_operands_lossy(headers, limit: Optional[int] = None, scratch_bytes: Optional[int] = None, caps: Optional[Dict[int, int]] = None):
+    """webp_operands for files that may hold lossy frames: (tab int64 (n, 16), the composition rows of ALL frames; ltab int64 (nl, 16), the rows of
+    the VP8L frames; vtab int64 (nv, 8), the rows of the VP8 frames (csrc/vp8dec_core.h); lidx, vidx, each row's frame number; data; chunks
+    [(f0, f1, l0, l1, v0, v1, scratch words, ARGB words)]).  A frame's scratch and ARGB offsets count from its chunk's start, and both kinds of
+    frame share the two buffers."""
+    if not headers:
+        raise ValueError("decode_webp_frames: no frames")
+    for k, h in enumerate(headers):
+        if (h.width, h.height) != (headers[0].width, headers[0].height):
+            raise ValueError(f"decode_webp_frames: file {k} has a canvas of {h.width} x {h.height}; file 0 has {headers[0].width} x "
+                             f"{headers[0].height}: one call decodes one canvas size")
+    frames = [(f, k == 0, h.frames[k - 1] if k else None) for h in headers for k, f in enumerate(h.frames)]
+    frames = frames if limit is None else frames[:max(0, int(limit))]
+    if not frames:
+        raise ValueError("decode_webp_frames: no frames")
+    budget = (WEBPDEC_SCRATCH_BYTES if scratch_bytes is None else int(scratch_bytes)) // 4
+    tab = np.zeros((len(frames), WEBP_TAB), np.int64)
+    lrows, vrows, lidx, vidx = [], [], [], []
+    chunks, begin, f0, l0, v0, scr, pix = [], 0, 0, 0, 0, 0, 0
+    for k, (f, first, before) in enumerate(frames):
+        cap = vp8_frame_scratch_words(f) if f.lossy else max(webp_frame_scratch_words(f), ((caps or {}).get(k, 0) + 3) & ~3)
+        npix = f.width * f.height
+        if k > f0 and scr + cap + pix + npix > budget:
+            chunks.append((f0, k, l0, len(lrows), v0, len(vrows), scr, pix))
+            f0, l0, v0, scr, pix = k, len(lrows), len(vrows), 0, 0
+        t = tab[k]
+        t[_WD_X], t[_WD_Y], t[_WD_W], t[_WD_H] = f.x, f.y, f.width, f.height
+        t[_WD_BEGIN], t[_WD_END], t[_WD_SCR], t[_WD_CAP], t[_WD_PIX] = begin, begin + len(f.payload), scr, cap, pix
+        t[_WD_FLAGS] = _WD_BLEND * f.blend | _WD_KEY * f.key | _WD_FIRST * first
+        if before is not None and before.dispose:
+            t[_WD_FLAGS] |= _WD_PREV_DISPOSED
+            t[_WD_PX], t[_WD_PY], t[_WD_PW], t[_WD_PH] = before.x, before.y, before.width, before.height
+        if f.lossy:
+            vrows.append([begin, begin + len(f.payload), scr, cap, pix, f.width, f.height, 0])
+            vidx.append(k)
+        else:
+            lrows.append(t.copy())
+            lidx.append(k)
+        scr += cap
+        pix += npix
+        begin += len(f.payload)
+    chunks.append((f0, len(frames), l0, len(lrows), v0, len(vrows), scr, pix))
+    blob = b"".join(f.payload for f, _, _ in frames)
+    data = np.frombuffer(blob + bytes(16 + (-len(blob)) % 16), np.uint8)
+    ltab = np.array(lrows, np.int64).reshape(len(lrows), WEBP_TAB)
+    vtab = np.array(vrows, np.int64).reshape(len(vrows), VP8_TAB)
+    return tab, ltab, vtab, np.array(lidx, np.int64), np.array(vidx, np.int64), data, chunks
+
+
+def _decode_webp_headers_lossy(headers, device, out=None, limit=None, caps=None):
+    """_decode_webp_headers for headers of parse_webp(lossy=True): per set of launches, the VP8L frames go through decode and untransform, the VP8
+    frames through parse, reconstruct, filter and output, all into one ARGB buffer, and one compose draws them in file order."""
+    import torch
+    from . import hip
+    tab, ltab, vtab, lidx, vidx, blob, chunks = webp_operands_lossy(headers, limit, caps=caps)
+    if hip.WEBPDEC_TAB != WEBP_TAB or hip.VP8DEC_TAB != VP8_TAB:
+        raise RuntimeError(f"decode_webp_frames: the binding's table rows have {hip.WEBPDEC_TAB} and {hip.VP8DEC_TAB} words, this module builds "
+                           f"{WEBP_TAB} and {VP8_TAB}")
+    n, H, W = len(tab), headers[0].height, headers[0].width
+    dev = torch.device(device)
+    if out is None:
+        out = torch.empty((n, H, W, 3), device=dev, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W, 3) or not out.is_contiguous() or not out.is_cuda:
+        raise RuntimeError(f"decode_webp_frames: out must be contiguous uint8 ({n}, {H}, {W}, 3) on the device")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_data, d_tab = up(blob.copy()), up(tab)
+    d_ltab, d_vtab = (up(ltab) if len(ltab) else None), (up(vtab) if len(vtab) else None)
+    lstatus = torch.zeros((2, max(1, len(ltab))), device=dev, dtype=torch.int32)
+    vstatus = torch.zeros((4, max(1, len(vtab))), device=dev, dtype=torch.int32)
+    scratch = torch.empty((max(c[6] for c in chunks),), device=dev, dtype=torch.int32)
+    argb = torch.empty((max(c[7] for c in chunks),), device=dev, dtype=torch.int32)
+    carry = torch.empty((H, W), device=dev, dtype=torch.int32)                # the RGBA canvas, from one chunk to the next
+    for f0, f1, l0, l1, v0, v1, scr_words, argb_words in chunks:
+        if l1 > l0:
+            hip.webp_decode(d_data, d_ltab[l0:l1], scratch[:scr_words], out=lstatus[0, l0:l1])
+            hip.webp_untransform(d_ltab[l0:l1], scratch[:scr_words], out=(argb[:argb_words], lstatus[1, l0:l1]))
+        if v1 > v0:
+            hip.vp8dec_parse(d_data, d_vtab[v0:v1], scratch[:scr_words], out=vstatus[0, v0:v1])
+            hip.vp8dec_reconstruct(d_vtab[v0:v1], scratch[:scr_words], out=vstatus[1, v0:v1])
+            hip.vp8dec_filter(d_vtab[v0:v1], scratch[:scr_words], out=vstatus[2, v0:v1])
+            hip.vp8dec_output(d_vtab[v0:v1], scratch[:scr_words], argb[:argb_words], int((vtab[v0:v1, _V8D_W] * vtab[v0:v1, _V8D_H]).max()),
+                              out=vstatus[3, v0:v1])
+        hip.webp_compose(d_tab[f0:f1], argb[:argb_words], carry, H, W, out=out[f0:f1])
+    st = torch.cat([lstatus.reshape(-1), vstatus.reshape(-1)]).cpu().numpy()   # the one read of the status words (it also orders the launches)
+    lst, vst = st[:lstatus.numel()].reshape(2, -1)[:, :len(ltab)], st[lstatus.numel():].reshape(4, -1)[:, :len(vtab)]
+    if len(ltab) and (lst[0] < 0).any() and caps is None:                      # more prefix-code groups than the first allowance: once more
+        del scratch, argb, carry
+        return _decode_webp_headers_lossy(headers, device, out, limit, {int(lidx[r]): -int(lst[0, r]) for r in np.flatnonzero(lst[0] < 0)})
+    found = []                                                                 # (frame, text) of the first failure of each kind
+    for stage, name in ((0, "image data"), (1, "transforms")):
+        bad = np.flatnonzero(lst[stage]) if len(ltab) else np.zeros(0, np.int64)
+        if bad.size and not any(x[1] == "l" for x in found):
+            code = 11 if lst[stage, bad[0]] < 0 else int(lst[stage, bad[0]])
+            found.append((int(lidx[bad[0]]), "l", f"{name}: {WEBP_STATUS_TEXT.get(code, f'status {code}')}"))
+    for stage, name in ((0, "VP8 parse"), (1, "VP8 reconstruction"), (2, "VP8 loop filter"), (3, "VP8 output")):
+        bad = np.flatnonzero(vst[stage]) if len(vtab) else np.zeros(0, np.int64)
+        if bad.size and not any(x[1] == "v" for x in found):
+            code = int(vst[stage, bad[0]])
+            found.append((int(vidx[bad[0]]), "v", f"{name}: {VP8_STATUS_TEXT.get(code, f'status {code}')}"))
+    if found:
+        f, _, text = min(found)
+        raise RuntimeError(f"decode_webp_frames: frame {f}, {text}")
+    return out
+
+
+def read_frames_device(path, limit: Optional[int] = None, device="cuda", webp_lossy=False):
     """(L, H, W, 3) uint8 RGB frames of `path` on `device`, decoded there: a Motion-JPEG .avi (what video_out.write_avi writes, or any stock
     tool's `-c:v mjpeg`), a directory whose images are all .jpg / .jpeg, all .png or all .webp (sorted by name; a .png or .webp file gives its
     first frame), one .png / .apng file, animated or not (what video_out.write_apng / write_png write), one .gif file (what video_out.write_gif
-    or PIL writes), or one lossless .webp file, animated or not (what video_out.write_webp or PIL's lossless=True writes).  Everything else
-    raises: inputs.read_frames is the host route, and the caller chooses it."""
+    or PIL writes), or one lossless .webp file, animated or not (what video_out.write_webp or PIL's lossless=True writes).  With webp_lossy=True a
+    .webp file or a directory of .webp files may also hold lossy frames (`VP8 ` chunks: video_out.write_webp(webp_quality=Q), PIL's default), alone
+    or beside lossless ones; without it such a file raises as before.  Everything else raises: inputs.read_frames is the host route, and the
+    caller chooses it."""
     from .inputs import IMAGE_SUFFIXES, mjpeg_avi_frames
     p = Path(path)
     if not p.exists():
@@ -1009,14 +1178,14 @@ def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
                 h.streams, h.adlers = h.streams[:1], h.adlers[:1]
             return _decode_png_operands(png_batch_operands(None, heads), device)
         if {f.suffix.lower() for f in files} == {".webp"}:
-            heads = [parse_webp(f.read_bytes()) for f in (files if limit is None else files[:limit])]
+            heads = [parse_webp(f.read_bytes(), **({"lossy": True} if webp_lossy else {})) for f in (files if limit is None else files[:limit])]
             for h in heads:                                                   # a file of a directory is one frame, as for inputs.read_frames
                 h.frames = h.frames[:1]
             if not heads:
                 raise RuntimeError(f"read_frames_device: no frames in {p}")
             if len({(h.width, h.height) for h in heads}) > 1:
                 raise RuntimeError(f"read_frames_device: the .webp frames of {p} differ in size; use inputs.read_frames for such a directory")
-            return _decode_webp_headers(heads, device)
+            return _decode_webp_headers_lossy(heads, device) if webp_lossy else _decode_webp_headers(heads, device)
         other = [f.name for f in files if f.suffix.lower() not in (".jpg", ".jpeg")]
         if not files or other:
             raise RuntimeError(f"read_frames_device: {p} must hold .jpg / .jpeg frames only, .png frames only or .webp frames only "
@@ -1036,7 +1205,7 @@ def read_frames_device(path, limit: Optional[int] = None, device="cuda"):
     elif p.suffix.lower() == ".webp":
         if limit is not None and limit < 1:
             raise RuntimeError(f"read_frames_device: no frames in {p}")
-        return decode_webp_frames(p.read_bytes(), device, limit=limit)
+        return decode_webp_frames(p.read_bytes(), device, limit=limit, **({"lossy": True} if webp_lossy else {}))
     else:
         jpegs = mjpeg_avi_frames(p, limit) if p.suffix.lower() == ".avi" else None
         if jpegs is None:

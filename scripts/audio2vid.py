@@ -39,6 +39,10 @@ def parse_args():
     p.add_argument("-c", "--config", default="./configs/prompts/animation.yaml")
     p.add_argument("--image_path", type=str)
     p.add_argument("--audio_path", type=str)
+    p.add_argument("--decode_lossy_webp", action="store_true",
+                   help="a .webp --image_path, lossy (VP8 key frames) or lossless, is decoded on the GPU (mmgt_amd.video_in.decode_webp_frames "
+                        "with lossy=True, DESIGN 4n: PIL's bytes); without it, and for a file outside that decoder's scope (an alpha plane), "
+                        "PIL opens the image on the host as before")
     p.add_argument("--out_dir", type=str, default="scripts/output_videos")
     p.add_argument("--tem_dir", type=str, default="scripts/output_videos/temp")
     p.add_argument("-W", type=int, default=512)
@@ -244,9 +248,17 @@ def main():
 
     # ---- 5. Stage 2 (:484-498) + output path
     from PIL import Image
-    if a.image_path:
+    ref_img = None
+    if a.image_path and a.decode_lossy_webp and a.image_path.lower().endswith(".webp"):
+        from mmgt_amd.video_in import decode_webp_frames
+        try:
+            with open(a.image_path, "rb") as fh:
+                ref_img = Image.fromarray(decode_webp_frames([fh.read()], dev, limit=1, lossy=True)[0].cpu().numpy())
+        except ValueError as e:                                  # outside the device decoder's scope: the parser says why
+            print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
+    if ref_img is None and a.image_path:
         ref_img = Image.open(a.image_path).convert("RGB")
-    else:
+    elif ref_img is None:
         ref_img = Image.fromarray(((hash_uniform("a2v.ref", (a.H, a.W, 3), 0.5) + 0.5) * 255).clamp(0, 255).to(torch.uint8).numpy())
     t0 = time.time()
     out = pipe(ref_img, pose, audio_tensor.float(), full, face, lips, a.W, a.H, a.L, a.steps, a.cfg,

@@ -72,6 +72,10 @@ def parse_args():
                         ".avi, a directory of .jpg, of .png or of lossless .webp frames, a .png / .apng file, a .gif file or a lossless .webp file (animated or "
                         "not), decoded on the GPU (mmgt_amd.video_in) and resized to W x H there with PIL's bytes; the reference image is then "
                         "resized on the device too (a baseline .jpg, a .png or a lossless .webp is also decoded there)")
+    p.add_argument("--decode_lossy_webp", action="store_true",
+                   help="with --decoder device: lossy .webp inputs (VP8 key frames: --format webp --webp_quality Q, or any stock writer's .webp), "
+                        "alone or mixed with lossless frames, are decoded on the GPU too (mmgt_amd.video_in, DESIGN 4n); without it they go "
+                        "through the host route as before.  A lossy file with an alpha plane (ALPH) still goes through the host")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -162,12 +166,14 @@ def build_from_checkpoints(cfg_path, num_c, dev, dtype):
 
 def load_inputs(a, dev):
     """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG,
-    PNG / APNG, GIF and lossless WebP on the GPU (mmgt_amd.video_in) and keeps the frames there; the default goes through PIL on the host."""
+    PNG / APNG, GIF and lossless WebP (with --decode_lossy_webp: lossy WebP too) on the GPU (mmgt_amd.video_in) and keeps the frames there; the
+    default goes through PIL on the host."""
     from mmgt_amd import inputs
     device = getattr(a, "decoder", "pil") == "device"
     if device:
         from mmgt_amd.video_in import read_frames_device
-        read = lambda path: read_frames_device(path, a.L, dev)
+        lossy = {"webp_lossy": True} if getattr(a, "decode_lossy_webp", False) else {}
+        read = lambda path: read_frames_device(path, a.L, dev, **lossy)
     else:
         read = lambda path: inputs.read_frames(path, a.L)
     pose_frames = read(a.pose_path)
@@ -201,7 +207,7 @@ def load_ref_image(a, dev):
             data = fh.read()
         try:
             if suffix == ".webp":
-                return decode_webp_frames([data], dev, limit=1)[0]
+                return decode_webp_frames([data], dev, limit=1, **({"lossy": True} if getattr(a, "decode_lossy_webp", False) else {}))[0]
             return (decode_png_frames if suffix == ".png" else decode_jpeg_frames)([data], dev)[0]
         except ValueError as e:                                  # outside the device decoders' scope (progressive, CMYK, 16 bit, interlace, lossy WebP, ...): the parser says why
             print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
