@@ -441,6 +441,19 @@ int mmgt_jpegdec_idct(const short* coef, const int* tables, unsigned char* plane
 /* libjpeg's fancy chroma up-sampling (replication when the chroma plane is 1 or 2 samples wide) + YCbCr -> RGB, cropped -> out (n, H, W, 3)
  * uint8; one component: Y in all three channels. */
 int mmgt_jpegdec_color(const unsigned char* planes, unsigned char* out, int n, int H, int W, int ncomp, int hs, int vs, void* stream);
+/* ---- progressive JPEG (SOF2) entropy stage (csrc/jpegprog.hip, csrc/jpegprog_core.h): fills the coefficient buffer of mmgt_jpegdec_idct
+ * from the scans of n equally sized progressive frames; called once per dependency level of the batch, lowest first, with that level's restart
+ * segments.  Segment s = data[offsets[s], offsets[s + 1]) holds the units [seginfo[3 s + 1], seginfo[3 s + 2]) of scan seginfo[3 s]; a unit is
+ * a frame MCU in a scan of all components and one of the component's own ceil(w_c / 8) x ceil(h_c / 8) blocks, in raster order, in a scan of one.
+ * scaninfo: 16 int32 words per scan (frame, component count, three component indices, Ss, Se, Ah, Al, three DC table indices, the AC table index,
+ * three spare); huff: nhuff tables of 307 words each (MINCODE / MAXCODE / VALPTR / HUFFVAL as in a frame's table block), indexed by scaninfo.
+ * coef: (n, frame_blocks, 64) int16 in natural order, the layout of mmgt_jpegdec_entropy; zero_fill != 0 (the first call of a batch) zero-fills
+ * it on the stream first; later calls refine what earlier ones left, stream order being the only ordering.  status[s] = 0, or 1 a code longer
+ * than 16 bits, 2 a coefficient index past Se, 3 a size category outside the scan type's range, 4 an EOB run past the segment's last block,
+ * 5 data exhausted before the last block, 6 a descriptor outside the batch (nothing read).  Nothing is written outside the segment's own blocks. */
+int mmgt_jpegprog_entropy(const unsigned char* data, long long data_bytes, const long long* offsets, const int* seginfo, const int* scaninfo,
+                          const int* huff, short* coef, int* status, int n, int nseg, int nscan, int nhuff, int H, int W, int ncomp, int hs, int vs,
+                          int zero_fill, void* stream);
 /* ---- device image resize (csrc/resize.hip, csrc/resample_core.h): PIL's ImagingResample for 8-bit images, Image.resize with BILINEAR /
  * BICUBIC / LANCZOS, bit for bit.  in (n, Hs, Ws, C) uint8 interleaved, C = 1 or 3, every side 1 .. 16384, upscale or downscale.  The caller hands
  * in PIL's integer coefficient tables (mmgt_amd.conditioning.pil_resample_tables) per axis that changes: bounds[D][2] = (first tap, tap count) with

@@ -119,6 +119,8 @@ _SIGS = {
                                      c_int, c_int, c_int, c_void_p]),
     "mmgt_jpegdec_idct": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_jpegdec_color": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_jpegprog_entropy": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_resize_u8_workspace": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_longlong)]),
     "mmgt_resize_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                c_void_p, c_void_p, c_int, c_void_p]),
@@ -1253,6 +1255,24 @@ def jpegdec_entropy(data, offsets, seginfo, tables, n, H, W, ncomp, hs, vs):
     _check(lib().mmgt_jpegdec_entropy(_ptr(data), data.numel(), _ptr(offsets), _ptr(seginfo), _ptr(tables), _ptr(coef), _ptr(status), n, nseg,
                                       H, W, ncomp, hs, vs, _stream()), "mmgt_jpegdec_entropy")
     return coef, status
+
+
+def jpegprog_entropy(data, offsets, seginfo, scaninfo, huff, coef, status, H, W, ncomp, hs, vs, zero_fill):
+    """One dependency level of a progressive batch (csrc/jpegprog.hip): its restart segments into coef (n, frame_blocks, 64) int16, which the
+    first level's call (zero_fill) clears first and later ones refine; status (nseg,) int32.  include/mmgt_hip.h states the operands."""
+    _dev(data, offsets, seginfo, scaninfo, huff, coef, status)
+    fb, _ = jpegdec_sizes(H, W, ncomp, hs, vs)
+    nseg, n = seginfo.shape[0], coef.shape[0]
+    if (data.dtype != torch.uint8 or data.dim() != 1 or offsets.dtype != torch.int64 or offsets.shape != (nseg + 1,) or seginfo.dtype != torch.int32
+            or seginfo.shape != (nseg, 3) or scaninfo.dtype != torch.int32 or scaninfo.dim() != 2 or scaninfo.shape[1] != 16
+            or huff.dtype != torch.int32 or huff.dim() != 2 or huff.shape[1] != 307 or coef.dtype != torch.int16 or coef.shape != (n, fb, 64)
+            or status.dtype != torch.int32 or status.shape != (nseg,)
+            or not all(t.is_contiguous() for t in (data, offsets, seginfo, scaninfo, huff, coef, status))):
+        raise RuntimeError("jpegprog_entropy: expected data uint8 (bytes,), offsets int64 (nseg + 1,), seginfo int32 (nseg, 3), scaninfo int32 "
+                           f"(nscan, 16), huff int32 (nhuff, 307), coef int16 (n, {fb}, 64), status int32 (nseg,), all contiguous")
+    _check(lib().mmgt_jpegprog_entropy(_ptr(data), data.numel(), _ptr(offsets), _ptr(seginfo), _ptr(scaninfo), _ptr(huff), _ptr(coef), _ptr(status),
+                                       n, nseg, scaninfo.shape[0], huff.shape[0], H, W, ncomp, hs, vs, int(bool(zero_fill)), _stream()),
+           "mmgt_jpegprog_entropy")
 
 
 def jpegdec_idct(coef, tables, H, W, ncomp, hs, vs):

@@ -3,7 +3,9 @@
   parse_jpeg           the markers of one baseline JPEG file -> JpegHeader (geometry, tables, the restart segments' byte ranges); refuses on the
                        host, with a ValueError naming the feature, everything the kernels do not decode
   decode_jpeg_frames   a batch of equally sized JPEG files -> (n, H, W, 3) uint8 RGB on the device: Huffman decode, dequantiser + inverse DCT,
-                       chroma up-sampling and colour conversion run in csrc/jpegdec.hip, bit for bit libjpeg's (libjpeg-turbo's) default decode
+                       chroma up-sampling and colour conversion run in csrc/jpegdec.hip, bit for bit libjpeg's (libjpeg-turbo's) default decode;
+                       with progressive=True both also take progressive files (SOF2), whose scans fill the same coefficient buffer through
+                       csrc/jpegprog.hip, one launch per dependency level of the scan script (scan_levels, prog_batch_operands)
   parse_png            the chunks of one PNG / APNG file -> PngHeader (geometry, palette, every frame's raw deflate bytes and expected Adler-32);
                        refuses on the host, with a ValueError naming the feature, everything the kernels do not decode
   decode_png_frames    PNG / APNG files of one geometry -> (n, H, W, 3) uint8 RGB on the device: inflate, scanline reconstruction and expansion run
@@ -65,6 +67,8 @@ class JpegHeader:
     restart_interval: int                        # MCUs per restart interval, 0 = none
     scan_offset: int                             # first byte of the entropy-coded data
     segments: List[Tuple[int, int]] = field(default_factory=list)       # [start, end) of every restart segment, markers excluded
+    progressive: bool = False                    # SOF2 (parse_jpeg(..., progressive=True)): `scans` holds the file, the five fields above are unused
+    scans: List["JpegScan"] = field(default_factory=list)
 
     @property
     def mcu_rows(self):
@@ -95,11 +99,15 @@ def _check_huffman(bits, vals, what):
         raise ValueError(f"parse_jpeg: {what} counts {total} codes for {len(vals)} values")
 
 
-def parse_jpeg(data) -> JpegHeader:
-    """One baseline JPEG file (bytes; trailing bytes after EOI are ignored) -> JpegHeader.  ValueError for everything outside the decoder's scope."""
+def parse_jpeg(data, progressive=False) -> JpegHeader:
+    """One baseline JPEG file (bytes; trailing bytes after EOI are ignored) -> JpegHeader.  ValueError for everything outside the decoder's scope.
+    With progressive=True a progressive file (SOF2) parses too, into a header with `progressive` set and its `scans`; a baseline file
+    parses as without it."""
     data = bytes(data)
     if len(data) < 4 or data[:2] != b"\xff\xd8":
         raise ValueError("parse_jpeg: not a JPEG file (missing SOI)")
+    if progressive and _first_sof(data) == 0xC2:
+        return _parse_progressive(data)
     pos, n = 2, len(data)
     qtables, huffman, sof, sos, ri, adobe = {}, {}, None, None, 0, None
     while sos is None:
@@ -231,6 +239,294 @@ def parse_jpeg(data) -> JpegHeader:
     return h
 
 
+# ---- progressive files (SOF2) -----------------------------------------------------------------------------------------------------
+
+# csrc/jpegprog_core.h's status words and scan descriptor
+PROG_STATUS_TEXT = {1: "a Huffman code longer than 16 bits", 2: "a coefficient index past the scan's Se",
+                    3: "a size category outside the scan type's range", 4: "an EOB run past the segment's last block",
+                    5: "data exhausted before the last block", 6: "a segment or scan descriptor outside the batch"}
+PROG_SCAN_INTS = 16
+
+
+@dataclass
+class JpegScan:
+    comps: Tuple[int, ...]                       # component indices (positions in the frame header), in scan order
+    ss: int                                      # spectral band [ss, se] in zigzag positions
+    se: int
+    ah: int                                      # successive approximation: 0 in a first scan, else the Al the band stood at; al: its new Al
+    al: int
+    restart_interval: int                        # the DRI in force at this SOS, in MCUs of THIS scan; 0 = none
+    td: Tuple[int, ...]                          # per scan component: DC table id, AC table id
+    ta: Tuple[int, ...]
+    huffman: Dict[Tuple[int, int], Tuple[bytes, bytes]]      # the tables in force at this SOS: (class, id 0..3) -> (BITS, HUFFVAL)
+    units: int                                   # MCUs of this scan: the frame's when it interleaves all components, else the component's own blocks
+    level: int                                   # dependency level (scan_levels)
+    segments: List[Tuple[int, int]] = field(default_factory=list)       # [start, end) of every restart segment, markers excluded
+
+
+def scan_levels(scans) -> List[int]:
+    """Dependency levels of a progressive file's scans, given as (components, Ss, Se) in file order: 0 for a scan that shares no (component,
+    coefficient) pair with an earlier one, else 1 + the largest level among the earlier scans that do.  Scans of one level touch disjoint
+    coefficients and may run in any order, after all scans of lower levels."""
+    last, out = {}, []
+    for comps, ss, se in scans:
+        pairs = [(c, k) for c in comps for k in range(ss, se + 1)]
+        level = 1 + max((last.get(p, -1) for p in pairs), default=-1)
+        for p in pairs:
+            last[p] = level
+        out.append(level)
+    return out
+
+
+def _first_sof(data):
+    """The marker of the file's first frame header (0xC0 .. 0xCF without DHT / JPG / DAC), or None: a walk over the header segments only."""
+    pos, n = 2, len(data)
+    while pos + 4 <= n and data[pos] == 0xFF:
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        if pos >= n:
+            return None
+        m = data[pos]
+        pos += 1
+        if 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return m
+        if m in (0xD9, 0xDA):
+            return None
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        pos += int.from_bytes(data[pos:pos + 2], "big")
+    return None
+
+
+def _parse_progressive(data) -> JpegHeader:
+    """parse_jpeg for a file whose frame header is SOF2: every scan with the tables and restart interval in force at its SOS."""
+    n = len(data)
+    a = np.frombuffer(data, np.uint8)
+    marks_at = np.flatnonzero((a[:-1] == 0xFF) & (a[1:] != 0) & (a[1:] != 0xFF))          # every 0xFF that a marker byte follows
+    qtables, huffman, sof, ri, adobe, scans, pos = {}, {}, None, 0, None, [], 2
+    geom = None                                                                           # set at the first SOS
+    bits_at = {}                                                                          # (component, zigzag position) -> the Al it stands at
+    while True:
+        if pos + 2 > n:
+            raise ValueError("parse_jpeg: missing EOI (the file ends after a scan)" if scans else
+                             "parse_jpeg: missing SOS (the file ends in its headers)" if sof else "parse_jpeg: missing SOF (the file ends in its headers)")
+        if data[pos] != 0xFF:
+            raise ValueError(f"parse_jpeg: expected a marker at byte {pos}")
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        if pos >= n:
+            continue
+        m = data[pos]
+        pos += 1
+        if m == 0xD9:
+            if not scans:
+                raise ValueError("parse_jpeg: missing SOS (EOI before any scan)" if sof else "parse_jpeg: missing SOF (EOI before any frame header)")
+            break
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            if scans:
+                raise ValueError("parse_jpeg: restart marker out of sequence (between two scans)")
+            continue
+        if pos + 2 > n:
+            continue
+        length = int.from_bytes(data[pos:pos + 2], "big")
+        body = data[pos + 2:pos + length]
+        if length < 2 or pos + length > n:
+            raise ValueError(f"parse_jpeg: segment {m:#04x} at byte {pos - 2} runs past the end of the file")
+        pos += length
+        if m == 0xDB:
+            if scans:
+                raise ValueError("parse_jpeg: a DQT after the first scan of a progressive file is not decoded (the library latches a component's "
+                                 "quantiser at that component's first scan)")
+            k = 0
+            while k < len(body):
+                pq, tid = body[k] >> 4, body[k] & 15
+                if pq != 0:
+                    raise ValueError("parse_jpeg: 16-bit quantiser tables are not decoded (8-bit DQT only)")
+                if tid > 3 or k + 65 > len(body):
+                    raise ValueError("parse_jpeg: bad DQT segment")
+                q = np.zeros(64, np.int32)
+                q[ZIGZAG] = np.frombuffer(body[k + 1:k + 65], np.uint8)
+                qtables[tid] = q
+                k += 65
+        elif m == 0xC2:
+            if sof is not None:
+                raise ValueError("parse_jpeg: more than one SOF")
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise ValueError("parse_jpeg: bad SOF2 segment")
+            sof = body
+        elif m == 0xC0:
+            raise ValueError("parse_jpeg: more than one SOF")
+        elif m in _SOF_NAMES:
+            raise ValueError(f"parse_jpeg: {_SOF_NAMES[m]} JPEG (SOF{m - 0xC0}) is not decoded")
+        elif m == 0xDC:
+            raise ValueError("parse_jpeg: a DNL segment (the number of lines defined after the first scan) is not decoded")
+        elif m == 0xC4:
+            k = 0
+            while k < len(body):
+                tc, th = body[k] >> 4, body[k] & 15
+                if tc > 1 or th > 3 or k + 17 > len(body):
+                    raise ValueError("parse_jpeg: bad DHT segment (classes 0 - 1, tables 0 - 3)")
+                bits = body[k + 1:k + 17]
+                cnt = sum(bits)
+                vals = body[k + 17:k + 17 + cnt]
+                _check_huffman(bits, vals, f"DHT table {tc}/{th}")
+                huffman[(tc, th)] = (bits, vals)
+                k += 17 + cnt
+        elif m == 0xDD:
+            if len(body) != 2:
+                raise ValueError("parse_jpeg: bad DRI segment")
+            ri = int.from_bytes(body, "big")
+        elif m == 0xEE and body[:5] == b"Adobe" and len(body) >= 12:
+            adobe = body[11]
+        elif m == 0xDA:
+            if sof is None:
+                raise ValueError("parse_jpeg: missing SOF (SOS before any frame header)")
+            if geom is None:
+                geom = _progressive_frame(sof, adobe, qtables)
+            width, height, ncomp, hs, vs, ids, tq = geom
+            ns = body[0] if body else 0
+            if ns < 1 or len(body) != 4 + 2 * ns:
+                raise ValueError("parse_jpeg: bad SOS segment")
+            try:
+                comps = tuple(ids.index(body[1 + 2 * i]) for i in range(ns))
+            except ValueError:
+                raise ValueError(f"parse_jpeg: scan {len(scans)} names a component the frame does not have") from None
+            td, ta = tuple(body[2 + 2 * i] >> 4 for i in range(ns)), tuple(body[2 + 2 * i] & 15 for i in range(ns))
+            ss, se, ah, al = body[1 + 2 * ns], body[2 + 2 * ns], body[3 + 2 * ns] >> 4, body[3 + 2 * ns] & 15
+            what = f"parse_jpeg: scan {len(scans)} (components {list(comps)}, Ss {ss}, Se {se}, Ah {ah}, Al {al})"
+            if ss > se or se > 63 or (ss == 0 and se != 0) or al > 13 or (ah != 0 and al != ah - 1):
+                raise ValueError(f"{what} is no legal progression (Ss <= Se <= 63, a DC scan has Se 0, Al <= 13, a refinement has Al = Ah - 1)")
+            if ss > 0 and ns != 1:
+                raise ValueError(f"{what} is no legal progression: an AC scan holds one component")
+            if ns > 1 and comps != tuple(range(ncomp)):
+                raise ValueError(f"{what}: a scan of several components that are not all of the frame's in order is not decoded")
+            for c in comps:
+                if ss > 0 and (c, 0) not in bits_at:
+                    raise ValueError(f"{what} is no legal progression: an AC scan of component {c} before that component's DC first scan")
+                for k in range(ss, se + 1):
+                    cur = bits_at.get((c, k))
+                    if cur is None and ah != 0:
+                        raise ValueError(f"{what} is no legal progression: the first scan of coefficient {k} of component {c} has Ah != 0")
+                    if cur is not None and ah == 0:
+                        raise ValueError(f"{what} is no legal progression: coefficient {k} of component {c} is sent twice at the same precision")
+                    if cur is not None and ah != cur:
+                        raise ValueError(f"{what} is no legal progression: a refinement with Ah {ah} of coefficient {k} of component {c}, "
+                                         f"which stands at Al {cur}")
+                    bits_at[(c, k)] = al
+            for i, c in enumerate(comps):
+                need = [(0, td[i])] if ss == 0 and ah == 0 else [] if ss == 0 else [(1, ta[i])]
+                for key in need:
+                    if key[1] > 3 or key not in huffman:
+                        raise ValueError(f"{what} names {'AC' if key[0] else 'DC'} Huffman table {key[1]}, which no DHT has defined by that point")
+            if ns > 1:
+                units = (-(-height // (8 * vs))) * (-(-width // (8 * hs)))
+            else:
+                wc, hc = (width, height) if comps[0] == 0 else (-(-width // hs), -(-height // vs))
+                units = (-(-wc // 8)) * (-(-hc // 8))
+            scan = JpegScan(comps, ss, se, ah, al, ri, td, ta, dict(huffman), units, 0)
+            # the scan's entropy-coded data: up to the first marker that is no RSTn
+            first = int(np.searchsorted(marks_at, pos))
+            cand = a[marks_at[first:] + 1]
+            stop = np.flatnonzero((cand < 0xD0) | (cand > 0xD7))
+            if stop.size == 0:
+                raise ValueError("parse_jpeg: missing EOI (a scan is truncated)")
+            k = int(stop[0])
+            if k and ri == 0:
+                raise ValueError(f"{what}: restart marker out of sequence (no restart interval is in force)")
+            if not np.array_equal(cand[:k], 0xD0 + (np.arange(k) & 7)):
+                raise ValueError(f"{what}: restart marker out of sequence")
+            need = -(-units // ri) if ri else 1
+            if k + 1 != need:
+                raise ValueError(f"{what} has {k + 1} restart intervals, {'fewer' if k + 1 < need else 'more'} than its {units} MCUs need ({need})")
+            at = marks_at[first:first + k + 1]
+            starts = np.concatenate([[pos], at[:k] + 2])
+            scan.segments = list(zip(starts.tolist(), at.tolist()))
+            scans.append(scan)
+            pos = int(at[k])
+        # APPn, COM and anything else with a length: skipped
+    if geom is None:
+        raise ValueError("parse_jpeg: missing SOS")
+    width, height, ncomp, hs, vs, ids, tq = geom
+    short = [(c, k, bits_at.get((c, k))) for c in range(ncomp) for k in range(64) if bits_at.get((c, k)) != 0]
+    if short:
+        c, k, cur = short[0]
+        raise ValueError(f"parse_jpeg: the scans do not bring every coefficient to full precision (coefficient {k} of component {c} "
+                         f"{'is never sent' if cur is None else f'stops at Al {cur}'}): the library decodes such a file with inter-block "
+                         "smoothing of the missing precision, which is not decoded here")
+    for s, level in zip(scans, scan_levels([(s.comps, s.ss, s.se) for s in scans])):
+        s.level = level
+    return JpegHeader(width, height, ncomp, hs, vs, tq, (0,) * ncomp, (0,) * ncomp, qtables, {}, 0, scans[0].segments[0][0], [], True, scans)
+
+
+def _progressive_frame(sof, adobe, qtables):
+    """The frame-level refusals of parse_jpeg on an SOF2 body -> (width, height, ncomp, hs, vs, component ids, quantiser ids)."""
+    precision, height, width, ncomp = sof[0], int.from_bytes(sof[1:3], "big"), int.from_bytes(sof[3:5], "big"), sof[5]
+    if precision != 8:
+        raise ValueError(f"parse_jpeg: {precision}-bit samples are not decoded (8-bit only)")
+    if ncomp == 4:
+        raise ValueError("parse_jpeg: four components (CMYK / YCCK) are not decoded")
+    if ncomp not in (1, 3):
+        raise ValueError(f"parse_jpeg: {ncomp} components are not decoded (one or three)")
+    if height < 1 or width < 1:
+        raise ValueError(f"parse_jpeg: frame size {width} x {height}")
+    if adobe == 0 and ncomp == 3:
+        raise ValueError("parse_jpeg: Adobe APP14 transform 0 (RGB stored without a colour transform) is not decoded")
+    ids = [sof[6 + 3 * c] for c in range(ncomp)]
+    if len(set(ids)) != ncomp:
+        raise ValueError("parse_jpeg: two components of the frame share an identifier")
+    samp = [(sof[7 + 3 * c] >> 4, sof[7 + 3 * c] & 15) for c in range(ncomp)]
+    tq = tuple(sof[8 + 3 * c] for c in range(ncomp))
+    if ncomp == 1:
+        hs, vs = 1, 1
+    else:
+        hs, vs = samp[0]
+        if samp[0] not in ((1, 1), (2, 1), (2, 2)) or samp[1] != (1, 1) or samp[2] != (1, 1):
+            raise ValueError(f"parse_jpeg: sampling factors {samp} are not decoded (luma 1x1, 2x1 or 2x2 with chroma 1x1)")
+    for c in range(ncomp):
+        if tq[c] not in qtables:
+            raise ValueError(f"parse_jpeg: component {c} names quantiser table {tq[c]}, which no DQT defines")
+    return width, height, ncomp, hs, vs, ids, tq
+
+
+def prog_batch_operands(jpegs, headers):
+    """Host-side operands of the progressive entropy stage for progressive files of one geometry (csrc/jpegprog_core.h):
+    dict(data uint8 (bytes,), offsets int64 (nseg + 1,), seginfo int32 (nseg, 3) = (scan, first unit, end unit), scaninfo int32 (nscan,
+    PROG_SCAN_INTS), huff int32 (nhuff, 307), tables int32 (n, TAB_INTS) for the idct launch, levels = the segment index at which each level starts
+    (nlevels + 1,), where = per segment (frame, scan of that file, restart segment of that scan)).  The segments are sorted by level, so one
+    level's launch takes a slice of offsets, seginfo and status.  Scans whose Huffman tables are equal share a table block."""
+    blocks, scaninfo, segs = {}, [], []
+
+    def block(table):
+        return blocks.setdefault((bytes(table[0]), bytes(table[1])), len(blocks))
+
+    for f, (j, h) in enumerate(zip(jpegs, headers)):
+        for k, s in enumerate(h.scans):
+            row = [0] * PROG_SCAN_INTS
+            row[0], row[1] = f, len(s.comps)
+            row[2:2 + len(s.comps)] = s.comps
+            row[5:9] = s.ss, s.se, s.ah, s.al
+            for i in range(len(s.comps)):
+                if s.ss == 0 and s.ah == 0:
+                    row[9 + i] = block(s.huffman[(0, s.td[i])])
+            if s.ss > 0:
+                row[12] = block(s.huffman[(1, s.ta[0])])
+            step = s.restart_interval or s.units
+            for r, (a, b) in enumerate(s.segments):
+                segs.append((s.level, len(scaninfo), r * step, min((r + 1) * step, s.units), j[a:b], (f, k, r)))
+            scaninfo.append(row)
+    segs.sort(key=lambda t: t[0])                                             # stable: (frame, scan, segment) order within a level
+    nlev = segs[-1][0] + 1
+    levels = np.searchsorted(np.asarray([t[0] for t in segs]), np.arange(nlev + 1)).astype(np.int64)
+    offsets = np.zeros(len(segs) + 1, np.int64)
+    np.cumsum([len(t[4]) for t in segs], out=offsets[1:])
+    if not blocks:                                                            # cannot happen for a parsed file (its first scan is a DC first scan)
+        blocks[(bytes(16), b"")] = 0
+    huff = np.stack([huffman_decode_arrays(bits, vals) for bits, vals in blocks])
+    return dict(data=np.frombuffer(b"".join(t[4] for t in segs) or b"\0", np.uint8), offsets=offsets,
+                seginfo=np.asarray([t[1:4] for t in segs], np.int32).reshape(-1, 3), scaninfo=np.asarray(scaninfo, np.int32).reshape(-1, PROG_SCAN_INTS),
+                huff=huff, tables=np.stack([frame_tables(h) for h in headers]), levels=levels, where=[t[5] for t in segs])
+
+
 def huffman_decode_arrays(bits, vals) -> np.ndarray:
     """BITS / HUFFVAL -> the int32 block of one table: MINCODE[0..16], MAXCODE[0..16] (-1: none), VALPTR[0..16] (T.81 F.2.2.3), HUFFVAL[0..255]."""
     out = np.zeros(_HUFF_INTS, np.int32)
@@ -286,16 +582,89 @@ def batch_operands(jpegs, headers=None):
     return headers, data, offsets, np.asarray(info, np.int32).reshape(-1, 3), np.stack([frame_tables(h) for h in headers])
 
 
-def decode_jpeg_frames(jpegs, device="cuda", out=None):
+def _same_geometry(headers):
+    for k, h in enumerate(headers):
+        if h.geometry != headers[0].geometry:
+            raise ValueError(f"decode_jpeg_frames: frame {k} is {h.width} x {h.height}, {h.ncomp} components, luma sampling {h.hs}x{h.vs}; frame 0 is "
+                             f"{headers[0].width} x {headers[0].height}, {headers[0].ncomp}, {headers[0].hs}x{headers[0].vs}: one call decodes one size")
+
+
+def _decode_progressive(jpegs, headers, frames, dev, out=None):
+    """Progressive files of one geometry -> (n, H, W, 3): one mmgt_jpegprog_entropy call per dependency level, then the baseline decoder's idct and
+    colour launches on the same coefficient layout.  `frames`: the files' indices in the caller's batch, for the error text."""
+    import torch
+    from . import hip
+    ops = prog_batch_operands(jpegs, headers)
+    H, W, ncomp, hs, vs = headers[0].geometry
+    fb, ti = hip.jpegdec_sizes(H, W, ncomp, hs, vs)
+    if ti != TAB_INTS:
+        raise RuntimeError(f"decode_jpeg_frames: the library's table block has {ti} words, this module builds {TAB_INTS}")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_data, d_offsets, d_seginfo, d_scaninfo, d_huff, d_tables = (up(ops[k].copy()) for k in ("data", "offsets", "seginfo", "scaninfo", "huff", "tables"))
+    nseg = len(ops["seginfo"])
+    coef = torch.empty((len(headers), fb, 64), device=dev, dtype=torch.int16)
+    status = torch.empty((nseg,), device=dev, dtype=torch.int32)
+    lv = ops["levels"].tolist()
+    for level, (a, b) in enumerate(zip(lv[:-1], lv[1:])):
+        hip.jpegprog_entropy(d_data, d_offsets[a:b + 1], d_seginfo[a:b], d_scaninfo, d_huff, coef, status[a:b], H, W, ncomp, hs, vs, zero_fill=level == 0)
+    planes = hip.jpegdec_idct(coef, d_tables, H, W, ncomp, hs, vs)
+    bad = torch.nonzero(status).flatten()[:1].cpu()                          # the one read of the status words (it also orders the launches)
+    if bad.numel():
+        s = int(bad[0])
+        code = int(status[s])
+        f, k, r = ops["where"][s]
+        raise RuntimeError(f"decode_jpeg_frames: frame {frames[f]}, scan {k}, restart segment {r}: {PROG_STATUS_TEXT.get(code, f'status {code}')}")
+    return hip.jpegdec_color(planes, H, W, ncomp, hs, vs, out=out)
+
+
+def _decode_mixed(jpegs, dev, out):
+    """decode_jpeg_frames(progressive=True): the batch split by kind, both kinds into the one output tensor."""
+    import torch
+    jpegs = [bytes(j) for j in jpegs]
+    headers = [parse_jpeg(j, progressive=True) for j in jpegs]
+    if not headers:
+        raise ValueError("decode_jpeg_frames: no frames")
+    _same_geometry(headers)
+    prog = [k for k, h in enumerate(headers) if h.progressive]
+    base = [k for k, h in enumerate(headers) if not h.progressive]
+    if not prog:
+        return _decode_baseline(batch_operands(jpegs, headers), dev, out)
+    if not base:
+        return _decode_progressive(jpegs, headers, prog, dev, out)
+    H, W = headers[0].height, headers[0].width
+    shape = (len(headers), H, W, 3)
+    if out is None:
+        out = torch.empty(shape, device=dev, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != dev:
+        raise RuntimeError(f"decode_jpeg_frames: out must be contiguous uint8 {shape} on {dev}")
+    a = _decode_baseline(batch_operands([jpegs[k] for k in base], [headers[k] for k in base]), dev, None, base)
+    b = _decode_progressive([jpegs[k] for k in prog], [headers[k] for k in prog], prog, dev)
+    out[torch.as_tensor(base, device=dev)] = a
+    out[torch.as_tensor(prog, device=dev)] = b
+    return out
+
+
+def decode_jpeg_frames(jpegs, device="cuda", out=None, progressive=False):
     """n baseline JPEG files of one size and sampling (quantiser and Huffman tables may differ per frame) -> (n, H, W, 3) uint8 RGB on `device`,
     contiguous; a greyscale file gives Y in all three channels (what Image.convert("RGB") gives).  `out`: a tensor of that shape to write into.
     Out-of-scope files raise ValueError before anything is launched; entropy-coded data that does not decode raises RuntimeError naming the
-    first bad frame and segment (the status words are read once per call), and no pixels are returned."""
+    first bad frame and segment (the status words are read once per call), and no pixels are returned.  With progressive=True the batch may hold
+    progressive files (SOF2), baseline files or both: a progressive file's scans fill the same coefficient buffer through csrc/jpegprog.hip, one
+    launch per dependency level of its scan script, and the rest of the decode is the baseline one."""
+    import torch
+    if progressive:
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        return _decode_mixed(jpegs, dev, out)
+    return _decode_baseline(batch_operands(jpegs), torch.device(device), out)
+
+
+def _decode_baseline(operands, dev, out, frames=None):
     import torch
     from . import hip
-    headers, data, offsets, seginfo, tables = batch_operands(jpegs)
+    headers, data, offsets, seginfo, tables = operands
     H, W, ncomp, hs, vs = headers[0].geometry
-    dev = torch.device(device)
     fb, ti = hip.jpegdec_sizes(H, W, ncomp, hs, vs)
     if ti != TAB_INTS:
         raise RuntimeError(f"decode_jpeg_frames: the library's table block has {ti} words, this module builds {TAB_INTS}")
@@ -308,7 +677,7 @@ def decode_jpeg_frames(jpegs, device="cuda", out=None):
         s = int(bad[0])
         code = int(status[s])
         f = int(seginfo[s, 0])
-        raise RuntimeError(f"decode_jpeg_frames: frame {f}, restart segment {s - int(np.searchsorted(seginfo[:, 0], f))}: "
+        raise RuntimeError(f"decode_jpeg_frames: frame {f if frames is None else frames[f]}, restart segment {s - int(np.searchsorted(seginfo[:, 0], f))}: "
                            f"{STATUS_TEXT.get(code, f'status {code}')}")
     return hip.jpegdec_color(planes, H, W, ncomp, hs, vs, out=out)
 
@@ -1158,13 +1527,14 @@ def _decode_webp_headers_lossy(headers, device, out=None, limit=None, caps=None)
     return out
 
 
-def read_frames_device(path, limit: Optional[int] = None, device="cuda", webp_lossy=False):
+def read_frames_device(path, limit: Optional[int] = None, device="cuda", webp_lossy=False, jpeg_progressive=False):
     """(L, H, W, 3) uint8 RGB frames of `path` on `device`, decoded there: a Motion-JPEG .avi (what video_out.write_avi writes, or any stock
     tool's `-c:v mjpeg`), a directory whose images are all .jpg / .jpeg, all .png or all .webp (sorted by name; a .png or .webp file gives its
     first frame), one .png / .apng file, animated or not (what video_out.write_apng / write_png write), one .gif file (what video_out.write_gif
     or PIL writes), or one lossless .webp file, animated or not (what video_out.write_webp or PIL's lossless=True writes).  With webp_lossy=True a
     .webp file or a directory of .webp files may also hold lossy frames (`VP8 ` chunks: video_out.write_webp(webp_quality=Q), PIL's default), alone
-    or beside lossless ones; without it such a file raises as before.  Everything else raises: inputs.read_frames is the host route, and the
+    or beside lossless ones; without it such a file raises as before.  With jpeg_progressive=True the .jpg / .jpeg files of a directory and the
+    frames of a Motion-JPEG .avi may be progressive (SOF2), alone or beside baseline ones; without it they raise as before.  Everything else raises: inputs.read_frames is the host route, and the
     caller chooses it."""
     from .inputs import IMAGE_SUFFIXES, mjpeg_avi_frames
     p = Path(path)
@@ -1213,4 +1583,4 @@ def read_frames_device(path, limit: Optional[int] = None, device="cuda", webp_lo
                                "directory of .jpg, .png or .webp frames; use inputs.read_frames for other inputs")
     if not jpegs:
         raise RuntimeError(f"read_frames_device: no frames in {p}")
-    return decode_jpeg_frames(jpegs, device)
+    return decode_jpeg_frames(jpegs, device, **({"progressive": True} if jpeg_progressive else {}))

@@ -43,6 +43,10 @@ def parse_args():
                    help="a .webp --image_path, lossy (VP8 key frames) or lossless, is decoded on the GPU (mmgt_amd.video_in.decode_webp_frames "
                         "with lossy=True, DESIGN 4n: PIL's bytes); without it, and for a file outside that decoder's scope (an alpha plane), "
                         "PIL opens the image on the host as before")
+    p.add_argument("--decode_progressive_jpeg", action="store_true",
+                   help="a .jpg / .jpeg --image_path, progressive (SOF2) or baseline, is decoded on the GPU (mmgt_amd.video_in.decode_jpeg_frames "
+                        "with progressive=True, DESIGN 4o: libjpeg-turbo's bytes); without it, and for a file outside that decoder's scope, "
+                        "PIL opens the image on the host as before")
     p.add_argument("--out_dir", type=str, default="scripts/output_videos")
     p.add_argument("--tem_dir", type=str, default="scripts/output_videos/temp")
     p.add_argument("-W", type=int, default=512)
@@ -254,6 +258,13 @@ def main():
         try:
             with open(a.image_path, "rb") as fh:
                 ref_img = Image.fromarray(decode_webp_frames([fh.read()], dev, limit=1, lossy=True)[0].cpu().numpy())
+        except ValueError as e:                                  # outside the device decoder's scope: the parser says why
+            print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
+    if a.image_path and a.decode_progressive_jpeg and a.image_path.lower().endswith((".jpg", ".jpeg")):
+        from mmgt_amd.video_in import decode_jpeg_frames
+        try:
+            with open(a.image_path, "rb") as fh:
+                ref_img = Image.fromarray(decode_jpeg_frames([fh.read()], dev, progressive=True)[0].cpu().numpy())
         except ValueError as e:                                  # outside the device decoder's scope: the parser says why
             print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
     if ref_img is None and a.image_path:

@@ -76,6 +76,10 @@ def parse_args():
                    help="with --decoder device: lossy .webp inputs (VP8 key frames: --format webp --webp_quality Q, or any stock writer's .webp), "
                         "alone or mixed with lossless frames, are decoded on the GPU too (mmgt_amd.video_in, DESIGN 4n); without it they go "
                         "through the host route as before.  A lossy file with an alpha plane (ALPH) still goes through the host")
+    p.add_argument("--decode_progressive_jpeg", action="store_true",
+                   help="with --decoder device: progressive .jpg inputs (SOF2: PIL's progressive=True, mozjpeg, any \"optimise for web\" export), "
+                        "alone or mixed with baseline frames, are decoded on the GPU too (mmgt_amd.video_in, DESIGN 4o); without it they go "
+                        "through the host route as before.  A progressive file that stops short of full precision still goes through the host")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--no-decode", action="store_true")
     p.add_argument("--clip-parallel", action="store_true",
@@ -166,13 +170,15 @@ def build_from_checkpoints(cfg_path, num_c, dev, dtype):
 
 def load_inputs(a, dev):
     """Pose frames and motion masks of the files `a` names -> (pose (1, 3, L, H, W), full, face, lips, L).  --decoder device reads Motion-JPEG,
-    PNG / APNG, GIF and lossless WebP (with --decode_lossy_webp: lossy WebP too) on the GPU (mmgt_amd.video_in) and keeps the frames there; the
+    PNG / APNG, GIF and lossless WebP (with --decode_lossy_webp: lossy WebP too; with --decode_progressive_jpeg: progressive JPEG too) on the GPU (mmgt_amd.video_in) and keeps the frames there; the
     default goes through PIL on the host."""
     from mmgt_amd import inputs
     device = getattr(a, "decoder", "pil") == "device"
     if device:
         from mmgt_amd.video_in import read_frames_device
         lossy = {"webp_lossy": True} if getattr(a, "decode_lossy_webp", False) else {}
+        if getattr(a, "decode_progressive_jpeg", False):
+            lossy["jpeg_progressive"] = True
         read = lambda path: read_frames_device(path, a.L, dev, **lossy)
     else:
         read = lambda path: inputs.read_frames(path, a.L)
@@ -196,7 +202,7 @@ def load_inputs(a, dev):
 
 def load_ref_image(a, dev):
     """The reference image as the pipeline takes it: a PIL image, or with --decoder device a uint8 (h, w, 3) tensor on the device -- a baseline
-    .jpg, a .png or a lossless .webp (its first frame) is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
+    .jpg (with --decode_progressive_jpeg: a progressive one too), a .png or a lossless .webp (its first frame) is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
     from PIL import Image
     if getattr(a, "decoder", "pil") != "device":
         return Image.open(a.image_path).convert("RGB")
@@ -208,7 +214,9 @@ def load_ref_image(a, dev):
         try:
             if suffix == ".webp":
                 return decode_webp_frames([data], dev, limit=1, **({"lossy": True} if getattr(a, "decode_lossy_webp", False) else {}))[0]
-            return (decode_png_frames if suffix == ".png" else decode_jpeg_frames)([data], dev)[0]
+            if suffix == ".png":
+                return decode_png_frames([data], dev)[0]
+            return decode_jpeg_frames([data], dev, **({"progressive": True} if getattr(a, "decode_progressive_jpeg", False) else {}))[0]
         except ValueError as e:                                  # outside the device decoders' scope (progressive, CMYK, 16 bit, interlace, lossy WebP, ...): the parser says why
             print(f"note: {os.path.basename(a.image_path)} is decoded on the host ({e})")
     import numpy as np
