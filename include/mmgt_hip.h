@@ -476,6 +476,17 @@ int mmgt_resize_u8(const unsigned char* in, unsigned char* tmp, unsigned char* o
 int mmgt_gif_histogram(const unsigned char* frames, unsigned int* hist, int n, int H, int W, void* stream);
 /* idx (n, H, W) u8 = lut[bin(pixel)], lut u8[32768] (video_out.gif_lut: the nearest palette entry of each bin centre).  No dithering. */
 int mmgt_gif_index(const unsigned char* frames, const unsigned char* lut, unsigned char* idx, int n, int H, int W, void* stream);
+/* idx (n, H, W) u8 under Floyd-Steinberg error diffusion (csrc/gif_dither_core.h states the rule; raster order, integer, per frame): the pixel plus
+ * the diffused error is clamped, looked up in lut, and leaves its difference to palette (256, 3) u8 as error.  A frame is one workgroup that takes
+ * bands of mmgt_gif_dither_band() rows in sequence; frames of more than one band pass a row of errors through scratch, mmgt_gif_dither_scratch()
+ * bytes (4 n W, or 0 for a single band; scratch may then be null), 4-byte aligned, contents irrelevant.  idx needs no alignment. */
+int mmgt_gif_dither(const unsigned char* frames, const unsigned char* lut, const unsigned char* palette, unsigned char* idx, void* scratch,
+                    long long scratch_bytes, int n, int H, int W, void* stream);
+int mmgt_gif_dither_band(void);
+int mmgt_gif_dither_scratch(int n, int H, int W, long long* bytes);
+/* Frame differencing: out (n, H, W) u8 = 255 where idx equals the frame before at that pixel, else idx; frame 0 is compared with prev (H, W), the
+ * last frame of the launch before, or copied if prev is null.  idx and out are 4-byte aligned and distinct. */
+int mmgt_gif_delta(const unsigned char* idx, const unsigned char* prev, unsigned char* out, int n, int H, int W, void* stream);
 /* GIF LZW (minimum code size 8, codes of 9 .. 12 bits, Clear = 256, End-of-Information = 257) of every (frame, strip): strip s of a frame is its rows
  * s * strip_rows .. min(H, (s + 1) * strip_rows) - 1, strips = ceil(H / strip_rows) <= 2048.  The strip's bits go LSB-first to
  * out + (frame * strips + s) * out_stride, their count to bits[frame * strips + s].  Every strip codes with a dictionary of its own: strip 0 opens

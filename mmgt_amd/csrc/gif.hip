@@ -5,6 +5,9 @@
 //                         caller's zeroed table: every workgroup counts into its own 128 KB LDS table and adds the bins it touched with global
 //                         atomics (integer adds: the result does not depend on the order).
 //  * mmgt_gif_index       idx = lut[bin(pixel)] with the 32 KB table in LDS; four pixels (three words in, one word out) per thread.  No dithering.
+//  * mmgt_gif_dither      the index map under Floyd-Steinberg error diffusion against the palette (csrc/gif_dither_core.h: rule and schedule); one
+//                         single-wave workgroup per frame, a lane per row of a band of 64 rows, each row two pixels behind the row above.
+//  * mmgt_gif_delta       frame differencing: 255 where a pixel's index equals the frame before's.
 //  * mmgt_gif_lzw         GIF's variable-width LZW, minimum code size 8.  One single-wave workgroup per (frame, strip of strip_rows image rows); lane 0
 //                         codes (LZW is a serial recurrence over the pixels), the other lanes stage pixels into LDS and clear the dictionary.
 //                         The dictionary is an open-addressed hash table of 8192 words in LDS, entry = (prefix << 8 | byte) << 12 | code.
@@ -17,6 +20,7 @@
 //  * mmgt_gif_pack        joins a frame's strips at their bit offsets (exclusive prefix sum of bits) and cuts the bytes into data sub-blocks:
 //                         a length byte before every 255 bytes, then the 0x00 terminator.  sizes[frame] = bytes written.
 #include "common.h"
+#include "gif_dither_core.h"
 #include "mmgt_hip.h"
 
 namespace {
@@ -69,6 +73,113 @@ __global__ __launch_bounds__(256) void gif_index_kernel(const unsigned char* __r
       reinterpret_cast<unsigned*>(idx)[g] = i0 | i1 << 8 | i2 << 16 | i3 << 24;
     } else {
       for (size_t p = 4 * g; p < npix; ++p) idx[p] = lut_s[bin_of(frames[3 * p], frames[3 * p + 1], frames[3 * p + 2])];
+    }
+  }
+}
+
+// ---- dithered index map ------------------------------------------------------------------------------------------------------------------------
+// One single-wave workgroup per frame; csrc/gif_dither_core.h states the rule and the schedule.  Lane r of a band of GDI_BAND rows stands at
+// x = t - 2 r in step t.  What it needs of the row above arrives from lane r - 1 by one DPP move per step (every lane executes it: the loop is
+// uniform, a lane outside the frame only computes nothing); lane 0 takes it from the carry row that lane 63 of the band before wrote, or zeros in the
+// first band.  Pixels and carry words are fetched a group of GDI_GROUP steps ahead, so that no step waits for global memory.
+__device__ __forceinline__ unsigned from_lane_above(unsigned v) {
+  // v_mov_b32 dpp wave_shr:1: lane l reads lane l - 1; lane 0 has no source and keeps `old`
+  return (unsigned)__builtin_amdgcn_update_dpp((int)GDI_ZERO, (int)v, 0x138, 0xf, 0xf, false);
+}
+
+__global__ __launch_bounds__(GDI_BAND) void gif_dither_kernel(const unsigned char* __restrict__ frames, const unsigned char* __restrict__ lut,
+                                                              const unsigned char* __restrict__ palette, unsigned char* __restrict__ idx, unsigned* carry,
+                                                              int H, int W, long long total) {
+  __shared__ __attribute__((aligned(16))) unsigned char lut_s[kBins];
+  __shared__ unsigned pal_s[256];
+  const int lane = threadIdx.x;
+  const long long frame = blockIdx.x;
+  for (int i = lane; i < kBins / 16; i += GDI_BAND) reinterpret_cast<u32x4*>(lut_s)[i] = reinterpret_cast<const u32x4*>(lut)[i];
+  for (int i = lane; i < 256; i += GDI_BAND) pal_s[i] = palette[3 * i] | (unsigned)palette[3 * i + 1] << 8 | (unsigned)palette[3 * i + 2] << 16;
+  __syncthreads();
+  unsigned* cr = carry + frame * W;                                // touched only if the frame has more than one band
+  for (int row0 = 0; row0 < H; row0 += GDI_BAND) {
+    const int rows = min((int)GDI_BAND, H - row0);
+    const bool first = row0 == 0, more = row0 + GDI_BAND < H;
+    const bool has_row = lane < rows, reads_carry = lane == 0 && !first;
+    const long long rowpix = (frame * H + row0 + lane) * W;        // of a lane without a row: never used
+    const long steps = gdi_band_steps(W, rows);
+    GdiLane s;
+    gdi_lane_reset(&s, reads_carry ? cr[0] : GDI_ZERO);
+    unsigned cur[3], raw[4] = {0u, 0u, 0u, 0u};                    // this group's pixels; the words that hold the next group's, in flight
+    unsigned ccur[GDI_GROUP], cnxt[GDI_GROUP];
+    for (int k = 0; k < GDI_GROUP; ++k) ccur[k] = cnxt[k] = GDI_ZERO;
+    const int shift = gdi_shift(3 * (rowpix - 2 * lane));          // group 0 is x = -2 lane .. 3 - 2 lane
+    if (has_row && lane < 2) gdi_fetch16(frames, 3 * (rowpix - 2 * lane), total, raw);
+    gdi_align12(raw, shift, cur);
+    if (reads_carry)
+      for (int k = 0; k < GDI_GROUP; ++k)
+        if (k + 1 < W) ccur[k] = cr[k + 1];
+    // A group's results are stored when the NEXT group begins, ahead of that group's loads: the wait for the loads at a group's end is a wait for
+    // everything in flight (the stores stand in branches, so they cannot be counted), and by then these stores are four steps old.
+    unsigned done_idx = 0u, done_err[GDI_GROUP];                   // the group's four indices, a byte each, and the errors they left
+    for (int k = 0; k < GDI_GROUP; ++k) done_err[k] = GDI_ZERO;
+    auto store_group = [&](long t) {                               // t: the group's first step
+#pragma unroll
+      for (int k = 0; k < GDI_GROUP; ++k) {
+        const int x = gdi_x(t + k, lane);
+        if (has_row && x >= 0 && x < W) {
+          idx[rowpix + x] = (unsigned char)(done_idx >> (8 * k));
+          if (more && lane == GDI_BAND - 1) cr[x] = done_err[k];
+        }
+      }
+    };
+    for (long t0 = 0; t0 < steps; t0 += GDI_GROUP) {
+      if (t0 > 0) store_group(t0 - GDI_GROUP);
+      const long x1 = gdi_x(t0 + GDI_GROUP, lane);                 // the next group: x1 .. x1 + 3
+      if (has_row && x1 + GDI_GROUP > 0 && x1 < W) gdi_fetch16(frames, 3 * (rowpix + x1), total, raw);
+      if (reads_carry)
+        for (int k = 0; k < GDI_GROUP; ++k) cnxt[k] = x1 + k + 1 < W ? cr[x1 + k + 1] : GDI_ZERO;
+      done_idx = 0u;
+#pragma unroll
+      for (int k = 0; k < GDI_GROUP; ++k) {
+        const int x = gdi_x(t0 + k, lane);
+        const bool active = has_row && x >= 0 && x < W;
+        const unsigned above = from_lane_above(s.out);
+        const unsigned in = lane == 0 ? ccur[k] : above;
+        unsigned r, g, b;
+        gdi_pixel(cur, k, &r, &g, &b);
+        const int i = gdi_lane_step(&s, in, active, r, g, b, lut_s, pal_s);
+        done_idx |= (unsigned)(i & 255) << (8 * k);
+        done_err[k] = s.out;
+      }
+      gdi_align12(raw, shift, cur);                                // the first use of what the loads returned
+      for (int k = 0; k < GDI_GROUP; ++k) {
+        // an empty statement that "changes" the word: without it hipcc copies the registers the carry loads write to right behind the loads,
+        // and that copy waits for every load in flight, the pixels' among them
+        asm volatile("" : "+v"(cnxt[k]));
+        ccur[k] = cnxt[k];
+      }
+    }
+    store_group((steps - 1) / GDI_GROUP * GDI_GROUP);
+    __syncthreads();                                             // the carry row lane 63 wrote is read by lane 0 in the next band
+  }
+}
+
+// ---- frame differencing ------------------------------------------------------------------------------------------------------------------------
+// out = 255 where a pixel's index equals the frame before's, else the index.  Pixel q of the clip is compared with pixel q - plane; the first frame
+// with `prev` (the last frame of the launch before), or with nothing.  Thread g takes pixels 4 g .. 4 g + 3.
+__device__ __forceinline__ unsigned delta_byte(unsigned cur, int before) { return (int)cur == before ? 255u : cur; }
+
+__global__ __launch_bounds__(256) void gif_delta_kernel(const unsigned char* __restrict__ idx, const unsigned char* __restrict__ prev,
+                                                        unsigned char* __restrict__ out, size_t npix, size_t plane) {
+  const size_t groups = (npix + 3) / 4;
+  const size_t step = (size_t)gridDim.x * 256;
+  for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += step) {
+    const size_t p = 4 * g;
+    if (p + 4 <= npix && p >= plane && (plane & 3) == 0) {
+      const unsigned a = reinterpret_cast<const unsigned*>(idx)[g], b = *reinterpret_cast<const unsigned*>(idx + p - plane);
+      unsigned v = 0;
+      for (int k = 0; k < 4; ++k) v |= delta_byte((a >> (8 * k)) & 255u, (int)((b >> (8 * k)) & 255u)) << (8 * k);
+      reinterpret_cast<unsigned*>(out)[g] = v;
+    } else {
+      for (size_t q = p; q < npix && q < p + 4; ++q)
+        out[q] = (unsigned char)delta_byte(idx[q], q >= plane ? (int)idx[q - plane] : prev ? (int)prev[q] : -1);
     }
   }
 }
@@ -270,6 +381,43 @@ extern "C" int mmgt_gif_index(const unsigned char* frames, const unsigned char* 
   const size_t want = ((npix + 3) / 4 + 4 * 256 - 1) / (4 * 256);
   const unsigned grid = (unsigned)(want < 1 ? 1 : want > 1024 ? 1024 : want);
   hipLaunchKernelGGL(gif_index_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, frames, lut, idx, npix);
+  MMGT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmgt_gif_dither_band(void) { return GDI_BAND; }
+
+// The carry row: one word per pixel of a row, per frame; frames of a single band need none.
+extern "C" int mmgt_gif_dither_scratch(int n, int H, int W, long long* bytes) {
+  MMGT_CHECK(bytes, "gif_dither_scratch: null output");
+  MMGT_CHECK(clip_ok(n, H, W), kBadClip, "gif_dither_scratch", n, H, W);
+  *bytes = H > GDI_BAND ? 4ll * n * W : 0;
+  return 0;
+}
+
+extern "C" int mmgt_gif_dither(const unsigned char* frames, const unsigned char* lut, const unsigned char* palette, unsigned char* idx, void* scratch,
+                               long long scratch_bytes, int n, int H, int W, void* stream) {
+  long long need = 0;
+  MMGT_CHECK(frames && lut && palette && idx, "gif_dither: null pointer");
+  if (mmgt_gif_dither_scratch(n, H, W, &need)) return 1;
+  MMGT_CHECK(need == 0 || (scratch && scratch_bytes >= need && aligned4(scratch)),
+             "gif_dither: %d frames of %d rows of %d pixels need %lld bytes of 4-byte aligned scratch for the carry rows, got %lld", n, H, W, need,
+             scratch ? scratch_bytes : 0ll);
+  MMGT_CHECK(aligned4(frames) && (reinterpret_cast<uintptr_t>(lut) & 15) == 0, "gif_dither: frames must be 4-byte aligned, lut 16-byte aligned");
+  hipLaunchKernelGGL(gif_dither_kernel, dim3((unsigned)n), dim3(GDI_BAND), 0, (hipStream_t)stream, frames, lut, palette, idx,
+                     static_cast<unsigned*>(scratch), H, W, 3ll * n * H * W);
+  MMGT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmgt_gif_delta(const unsigned char* idx, const unsigned char* prev, unsigned char* out, int n, int H, int W, void* stream) {
+  MMGT_CHECK(idx && out && idx != out, "gif_delta: null pointer, or out is idx");
+  MMGT_CHECK(clip_ok(n, H, W), kBadClip, "gif_delta", n, H, W);
+  MMGT_CHECK(aligned4(idx) && aligned4(out), "gif_delta: idx and out must be 4-byte aligned");
+  const size_t npix = (size_t)n * H * W;
+  const size_t want = ((npix + 3) / 4 + 4 * 256 - 1) / (4 * 256);
+  const unsigned grid = (unsigned)(want < 1 ? 1 : want > 1024 ? 1024 : want);
+  hipLaunchKernelGGL(gif_delta_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, idx, prev, out, npix, (size_t)H * W);
   MMGT_LAUNCH_CHECK();
   return 0;
 }

@@ -126,6 +126,10 @@ _SIGS = {
                                c_void_p, c_void_p, c_int, c_void_p]),
     "mmgt_gif_histogram": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_index": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_gif_dither": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_int, c_void_p]),
+    "mmgt_gif_dither_band": (c_int, []),
+    "mmgt_gif_dither_scratch": (c_int, [c_int, c_int, c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "mmgt_gif_delta": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "mmgt_gif_lzw": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_long, c_void_p]),
     "mmgt_gif_strip_stride": (c_int, [c_int, c_int, ctypes.POINTER(c_long)]),
     "mmgt_gif_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_long, c_long, c_void_p]),
@@ -1333,6 +1337,58 @@ def gif_index(frames, lut):
     idx = torch.empty((n, H, W), device=frames.device, dtype=torch.uint8)
     _check(lib().mmgt_gif_index(_ptr(frames), _ptr(lut), _ptr(idx), n, H, W, _stream()), "mmgt_gif_index")
     return idx
+
+
+def gif_dither_band():
+    """Rows of one band of mmgt_gif_dither (csrc/gif_dither_core.h: GDI_BAND): a taller frame passes a row of errors from band to band."""
+    return lib().mmgt_gif_dither_band()
+
+
+def gif_dither_scratch_bytes(n, H, W):
+    """Bytes of scratch that gif_dither needs for n frames of H x W: the carry rows, none for frames of a single band."""
+    v = ctypes.c_longlong(0)
+    _check(lib().mmgt_gif_dither_scratch(int(n), int(H), int(W), ctypes.byref(v)), "mmgt_gif_dither_scratch")
+    return v.value
+
+
+def gif_dither(frames, lut, palette, out=None, scratch=None):
+    """idx (n, H, W) uint8 under Floyd-Steinberg error diffusion against `palette` (256, 3) uint8 (csrc/gif_dither_core.h states the rule); lut as
+    for gif_index.  `out` (n, H, W) uint8 contiguous (any alignment) and `scratch` uint8 (>= gif_dither_scratch_bytes, contents irrelevant) to write
+    into."""
+    n, H, W = _rgb_frames(frames, "gif_dither")
+    _dev(lut, palette, out, scratch)
+    if lut.dtype != torch.uint8 or tuple(lut.shape) != (GIF_BINS,) or not lut.is_contiguous():
+        raise RuntimeError("gif_dither: lut must be contiguous uint8 (32768,)")
+    if palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or not palette.is_contiguous():
+        raise RuntimeError("gif_dither: palette must be contiguous uint8 (256, 3)")
+    if out is None:
+        out = torch.empty((n, H, W), device=frames.device, dtype=torch.uint8)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n, H, W) or not out.is_contiguous():
+        raise RuntimeError(f"gif_dither: out must be contiguous uint8 ({n}, {H}, {W})")
+    if scratch is None:
+        scratch = torch.empty((max(4, gif_dither_scratch_bytes(n, H, W)),), device=frames.device, dtype=torch.uint8)
+    if scratch.dtype != torch.uint8 or scratch.dim() != 1 or not scratch.is_contiguous():
+        raise RuntimeError("gif_dither: scratch must be contiguous uint8 (bytes,)")
+    _check(lib().mmgt_gif_dither(_ptr(frames), _ptr(lut), _ptr(palette), _ptr(out), _ptr(scratch), scratch.numel(), n, H, W, _stream()),
+           "mmgt_gif_dither")
+    return out
+
+
+def gif_delta(idx, prev=None, out=None):
+    """Frame differencing of an index map (n, H, W) uint8: 255 where a pixel equals the frame before, else the index.  Frame 0 is compared with
+    `prev` (H, W), the last frame of the part of the clip before this one, or copied if there is none."""
+    _dev(idx, prev, out)
+    if idx.dtype != torch.uint8 or idx.dim() != 3 or not idx.is_contiguous():
+        raise RuntimeError("gif_delta: idx must be contiguous uint8 (n, H, W)")
+    n, H, W = idx.shape
+    if prev is not None and (prev.dtype != torch.uint8 or tuple(prev.shape) != (H, W) or not prev.is_contiguous()):
+        raise RuntimeError(f"gif_delta: prev must be contiguous uint8 ({H}, {W})")
+    if out is None:
+        out = torch.empty_like(idx)
+    if out.dtype != torch.uint8 or out.shape != idx.shape or not out.is_contiguous():
+        raise RuntimeError(f"gif_delta: out must be contiguous uint8 {tuple(idx.shape)}")
+    _check(lib().mmgt_gif_delta(_ptr(idx), _ptr(prev), _ptr(out), n, H, W, _stream()), "mmgt_gif_delta")
+    return out
 
 
 def gif_strip_stride(W, strip_rows):

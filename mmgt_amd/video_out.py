@@ -5,7 +5,8 @@ encodes with PyAV / libx264, which is not part of this build: .gif goes through 
 .npy stores the raw uint8 frames, .mp4 raises.  .avi is this build's video file: baseline JPEG frames encoded on the device
 (csrc/mjpeg.hip; encode_jpeg_frames) in a RIFF AVI 1.0 container with an optional PCM sound track (write_avi).  gif_encoder="device" is a second,
 opt-in .gif writer: one palette for the clip (gif_palette, gif_lut), index map, LZW and sub-block packing on the device (csrc/gif.hip;
-encode_gif_frames) and the GIF89a container here (write_gif).  .apng / .png are the lossless output: scanline filters and deflate on the device
+encode_gif_frames) and the GIF89a container here (write_gif); gif_dither="fs" adds Floyd-Steinberg dithering against that palette and
+gif_delta=True frame differencing through a transparent index, both on the device too.  .apng / .png are the lossless output: scanline filters and deflate on the device
 (csrc/png.hip; encode_png_frames), Huffman code lengths, block headers and the PNG / APNG chunks here (write_png, write_png_sequence, write_apng).
 .webp is the second lossless output, WebP lossless / animated WebP: subtract green, predictor choice and prefix coding on the device (csrc/webp.hip;
 encode_webp_frames), the five codes of a frame, its header and the RIFF chunks here (webp_prefix_code, webp_frame_header, write_webp).
@@ -224,7 +225,7 @@ def _gif_hist(hist):
     return h
 
 
-def gif_palette(hist) -> np.ndarray:
+def gif_palette(hist, colors=256) -> np.ndarray:
     """(32768,) pixel counts per bin -> (256, 3) uint8 palette by median cut over the occupied bins, in integer arithmetic only (the same table on
     every call and every host).  A bin has the coordinates (r, g, b) = (bin >> 10, bin >> 5 & 31, bin & 31) and the centre 8 i + 4 per channel.
 
@@ -234,7 +235,11 @@ def gif_palette(hist) -> np.ndarray:
     before B on a tie; with c(v) the box's pixels at coordinate v of that axis and T their sum, the cut m is the smallest v with
     2 (c(min) + ... + c(v)) >= T, lowered to max - 1 if it is max; bins with coordinate <= m keep the box's index, the others become the box with the
     next free index.  Entry k is, per channel, the count-weighted mean of the centres of box k's bins, rounded half up:
-    floor((2 sum(c (8 i + 4)) + sum c) / (2 sum c))."""
+    floor((2 sum(c (8 i + 4)) + sum c) / (2 sum c)).
+
+    colors=255 keeps entry 255 out of it (zero), for the transparent index of frame differencing: "up to 255 occupied bins", "until there are 255
+    boxes"."""
+    colors = _gif_colors(colors)
     h = _gif_hist(hist)
     occ = np.flatnonzero(h)
     pal = np.zeros((256, 3), np.uint8)
@@ -242,7 +247,7 @@ def gif_palette(hist) -> np.ndarray:
         raise ValueError("gif_palette: the histogram is empty")
     coord = np.stack([occ >> 10, (occ >> 5) & 31, occ & 31], axis=1).astype(np.int64)       # (bins, 3)
     cnt = h[occ]
-    if occ.size <= 256:
+    if occ.size <= colors:
         pal[:occ.size] = 8 * coord + 4
         return pal
 
@@ -256,7 +261,7 @@ def gif_palette(hist) -> np.ndarray:
 
     boxes = [np.arange(occ.size)]
     scores = [score(boxes[0])]
-    while len(boxes) < 256:
+    while len(boxes) < colors:
         best = max((k for k in range(len(boxes)) if scores[k] is not None), key=lambda k: (scores[k][0], -k))
         members, axis = boxes[best], scores[best][1]
         v = coord[members, axis]
@@ -279,6 +284,12 @@ def gif_palette(hist) -> np.ndarray:
     return pal
 
 
+def _gif_colors(colors):
+    if colors not in (255, 256):
+        raise ValueError(f"colors must be 256, or 255 to keep index 255 free, got {colors!r}")
+    return int(colors)
+
+
 def _gif_check_palette(palette):
     pal = np.asarray(palette)
     if pal.shape != (256, 3) or pal.dtype != np.uint8:
@@ -286,36 +297,55 @@ def _gif_check_palette(palette):
     return pal
 
 
-def gif_lut(palette) -> np.ndarray:
+def gif_lut(palette, colors=256) -> np.ndarray:
     """(256, 3) uint8 palette -> (32768,) uint8: for every bin the palette entry nearest to the bin's centre (8 r + 4, 8 g + 4, 8 b + 4) by squared
-    RGB distance, the lowest index on a tie."""
-    pal = _gif_check_palette(palette).astype(np.int32)
+    RGB distance, the lowest index on a tie.  colors=255 looks among entries 0 .. 254 only: no bin maps to index 255."""
+    colors = _gif_colors(colors)
+    pal = _gif_check_palette(palette).astype(np.int32)[:colors]
     centre = 8 * np.arange(32, dtype=np.int32) + 4
     d = [(centre[:, None] - pal[None, :, ch]) ** 2 for ch in range(3)]                       # (32, 256) each
-    dist = d[0][:, None, None, :] + d[1][None, :, None, :] + d[2][None, None, :, :]          # (32, 32, 32, 256)
-    return np.argmin(dist.reshape(GIF_BINS, 256), axis=1).astype(np.uint8)                   # argmin returns the first minimum
+    dist = d[0][:, None, None, :] + d[1][None, :, None, :] + d[2][None, None, :, :]          # (32, 32, 32, colors)
+    return np.argmin(dist.reshape(GIF_BINS, colors), axis=1).astype(np.uint8)                   # argmin returns the first minimum
 
 
-def encode_gif_frames(frames_u8, palette=None, strip_rows=None):
+def encode_gif_frames(frames_u8, palette=None, strip_rows=None, dither=None, delta=False):
     """(n, H, W, 3) uint8 RGB frames (a CUDA tensor, or host data that is uploaded) -> (palette (256, 3) uint8, n byte strings): each string is
     one frame's GIF image data as write_gif takes it, LZW-coded against `palette` and cut into data sub-blocks with the 0x00 terminator.  Colour
-    histogram, index map (nearest palette entry of the pixel's 5-bit bin, no dithering), LZW and packing run on the device (csrc/gif.hip); the host
-    builds palette and lookup table from the 128 KB histogram (gif_palette / gif_lut, skipped for the histogram if `palette` is given) and receives
-    the sizes and ONE buffer of finished bytes per set of launches.  The bytes are the same on every call."""
+    histogram, index map, LZW and packing run on the device (csrc/gif.hip); the host builds palette and lookup table from the 128 KB histogram
+    (gif_palette / gif_lut, skipped for the histogram if `palette` is given) and receives the sizes and ONE buffer of finished bytes per set of
+    launches.  The bytes are the same on every call.
+
+    dither=None: a pixel takes the palette entry of its 5-bit bin.  dither="fs": Floyd-Steinberg error diffusion against the palette, per frame
+    (mmgt_gif_dither; DESIGN.md 4d states the rule).  delta=True: frame differencing; the palette has 255 colours (entry 255 zero; one you supply
+    must have it so), and from the second frame on a pixel whose index equals the frame before's is written as 255, which write_gif(...,
+    transparent=255) declares transparent.  The comparison runs across the whole clip, also where it is split into sets of launches."""
     from . import hip
     x, n, H, W, strip_rows = _clip(frames_u8, "encode_gif_frames", max_side=65535, a_frame="a GIF frame", strip_rows=strip_rows,
                                    default_rows=GIF_STRIP_ROWS)
+    if dither not in (None, "fs"):
+        raise ValueError(f"encode_gif_frames: dither must be None or 'fs', got {dither!r}")
+    colors = 255 if delta else 256
     if palette is not None:
         palette = _gif_check_palette(palette).copy()
+        if delta and palette[255].any():
+            raise ValueError("encode_gif_frames: with delta=True index 255 is the transparent one: row 255 of the palette must be zero")
     x = _on_device(x)
     if palette is None:
-        palette = gif_palette(hip.gif_histogram(x).cpu().numpy().view(np.uint32))
-    lut = torch.from_numpy(gif_lut(palette)).to(x.device)
+        palette = gif_palette(hip.gif_histogram(x).cpu().numpy().view(np.uint32), colors)
+    lut = torch.from_numpy(gif_lut(palette, colors)).to(x.device)
+    pal_d = torch.from_numpy(palette).to(x.device) if dither else None
     strips = -(-H // strip_rows)
     stride = hip.gif_strip_stride(W, strip_rows)
     blobs = []
-    for part in _batches(x, GIF_SCRATCH_BYTES, H * W + strips * stride + hip.gif_packed_stride(strips, stride)):
-        packed, sizes = hip.gif_pack(*hip.gif_lzw(hip.gif_index(part, lut), strip_rows))
+    last = None                                                    # the index map of the frame before this set of launches
+    per_frame = H * W * (2 if delta else 1) + (4 * W if dither else 0) + strips * stride + hip.gif_packed_stride(strips, stride)
+    for part in _batches(x, GIF_SCRATCH_BYTES, per_frame):
+        if part.data_ptr() % 4:                                    # a later part of a clip whose frames are no multiple of 4 bytes
+            part = part.clone()
+        idx = hip.gif_dither(part, lut, pal_d) if dither else hip.gif_index(part, lut)
+        if delta:
+            idx, last = hip.gif_delta(idx, last), idx[-1]
+        packed, sizes = hip.gif_pack(*hip.gif_lzw(idx, strip_rows))
         sizes = sizes.tolist()
         if min(sizes) < 1:
             raise RuntimeError("encode_gif_frames: the packed frame did not fit its slot (mmgt_gif_pack)")
@@ -324,13 +354,18 @@ def encode_gif_frames(frames_u8, palette=None, strip_rows=None):
     return palette, blobs
 
 
-def write_gif(path, palette, frame_blobs, W, H, fps, loop=0):
+def write_gif(path, palette, frame_blobs, W, H, fps, loop=0, transparent=None):
     """GIF89a: header, logical screen descriptor with a 256-entry global colour table, the NETSCAPE2.0 loop extension (`loop` repetitions, 0 = for
     ever), per frame a graphic control extension (delay, no disposal, no transparency) and an image descriptor covering the screen with no local
     table, the LZW minimum code size 8 and the frame's data sub-blocks as encode_gif_frames returns them; then the trailer.  Returns the bytes
     written.  A GIF delay is a whole number of centiseconds, round(100 / fps): 25 fps is 4 cs exactly, but most rates are not expressible
-    (8 fps -> 12 cs = 8.33 fps, 30 fps -> 3 cs = 33.3 fps).  DESIGN.md 4d lists the fields."""
+    (8 fps -> 12 cs = 8.33 fps, 30 fps -> 3 cs = 33.3 fps).  DESIGN.md 4d lists the fields.
+
+    transparent = an index (255 for encode_gif_frames(..., delta=True)) writes the clip for frame differencing: every frame is left in place
+    (disposal 1), and from the second frame on that index is declared transparent, so a pixel coded with it keeps what the frames before drew."""
     pal = _gif_check_palette(palette)
+    if transparent is not None and not 0 <= int(transparent) <= 255:
+        raise ValueError(f"write_gif: transparent must be None or an index 0 .. 255, got {transparent!r}")
     blobs = [bytes(b) for b in frame_blobs]
     if not blobs:
         raise ValueError("write_gif: no frames")
@@ -345,11 +380,15 @@ def write_gif(path, palette, frame_blobs, W, H, fps, loop=0):
     out = [b"GIF89a", struct.pack("<HHBBB", int(W), int(H), 0xF7, 0, 0), pal.tobytes(),
            b"\x21\xff\x0bNETSCAPE2.0\x03\x01" + struct.pack("<H", loop) + b"\x00"]
     gce = b"\x21\xf9\x04" + struct.pack("<BHB", 0, delay, 0) + b"\x00"
+    gce_later = gce
+    if transparent is not None:                                    # packed: disposal 1 << 2, transparency flag 1
+        gce = b"\x21\xf9\x04" + struct.pack("<BHB", 0x04, delay, 0) + b"\x00"
+        gce_later = b"\x21\xf9\x04" + struct.pack("<BHB", 0x05, delay, int(transparent)) + b"\x00"
     desc = b"\x2c" + struct.pack("<HHHHB", 0, 0, int(W), int(H), 0) + b"\x08"
-    for b in blobs:
+    for k, b in enumerate(blobs):
         if not b or b[-1] != 0:
             raise ValueError("write_gif: a frame's data must be sub-blocks ending with the 0x00 terminator")
-        out += [gce, desc, b]
+        out += [gce if k == 0 else gce_later, desc, b]
     out.append(b"\x3b")
     body = b"".join(out)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -875,10 +914,16 @@ def write_webp(path, blobs, W, H, fps, loop=0, lossy=False):
     return _write(path, b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
-def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90, gif_encoder="pil", webp_quality=None):
-    """`quality` is the Motion-JPEG quality of .avi.  `webp_quality` = None writes .webp lossless; 0 .. 100 writes it lossy (VP8 key frames)."""
+def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=90, gif_encoder="pil", webp_quality=None, gif_dither=None,
+                     gif_delta=False):
+    """`quality` is the Motion-JPEG quality of .avi.  `webp_quality` = None writes .webp lossless; 0 .. 100 writes it lossy (VP8 key frames).
+    `gif_dither` ("fs": Floyd-Steinberg) and `gif_delta` (frame differencing through a transparent index) are options of gif_encoder="device"."""
     if gif_encoder not in ("pil", "device"):
         raise ValueError(f"gif_encoder must be 'pil' or 'device', got {gif_encoder!r}")
+    if gif_dither not in (None, "fs"):
+        raise ValueError(f"gif_dither must be None or 'fs', got {gif_dither!r}")
+    if gif_encoder == "pil" and (gif_dither is not None or gif_delta):
+        raise ValueError("gif_dither and gif_delta are options of gif_encoder='device'; gif_encoder='pil' writes what PIL writes")
     if webp_quality is not None and not 0 <= int(webp_quality) <= 100:
         raise ValueError(f"webp_quality must be None or 0 .. 100, got {webp_quality!r}")
     if rescale:
@@ -892,8 +937,8 @@ def save_videos_grid(videos, path: str, rescale=False, n_rows=6, fps=8, quality=
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     fmt = Path(path).suffix
     if fmt == ".gif" and gif_encoder == "device":
-        palette, blobs = encode_gif_frames(frames)
-        write_gif(path, palette, blobs, frames.shape[2], frames.shape[1], fps)
+        palette, blobs = encode_gif_frames(frames, dither=gif_dither, delta=bool(gif_delta))
+        write_gif(path, palette, blobs, frames.shape[2], frames.shape[1], fps, transparent=255 if gif_delta else None)
     elif fmt == ".gif":
         from PIL import Image
         pil = [Image.fromarray(f) for f in frames]

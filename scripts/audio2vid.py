@@ -76,6 +76,12 @@ def parse_args():
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
                         "on the device: mmgt_amd.video_out.encode_gif_frames)")
+    p.add_argument("--gif_dither", default="none", choices=["none", "fs"],
+                   help="with --gif_encoder device: fs = Floyd-Steinberg error diffusion against the clip's palette (smooth gradients stop banding; "
+                        "the file grows)")
+    p.add_argument("--gif_delta", action="store_true",
+                   help="with --gif_encoder device: frame differencing, a pixel that keeps its palette index from one frame to the next is written "
+                        "as the transparent index 255 (a palette of 255 colours)")
     p.add_argument("--wavlm", default="off", metavar="{off,random,PATH}",
                    help="WavLM-Large features of --audio_path as columns 0:1024 of the SMGA conditioning: off (hash-seeded stand-in, the default), "
                         "random (hash-seeded Large weights) or the path of a WavLM-Large.pt checkpoint")
@@ -293,7 +299,8 @@ def main():
         extra["files"] = len(write_png_sequence(path, encode_png_frames(v[0]), a.W, a.H))
     else:
         lossy = a.webp_quality if a.format == "webp" else None
-        save_videos_grid(v, path, n_rows=1, fps=a.fps or 25, gif_encoder=a.gif_encoder, webp_quality=lossy)
+        gif = dict(gif_dither=None if a.gif_dither == "none" else a.gif_dither, gif_delta=a.gif_delta) if a.format == "gif" else {}
+        save_videos_grid(v, path, n_rows=1, fps=a.fps or 25, gif_encoder=a.gif_encoder, webp_quality=lossy, **gif)
         if lossy is not None:
             extra["webp_quality"] = lossy
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,

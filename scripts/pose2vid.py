@@ -67,6 +67,12 @@ def parse_args():
     p.add_argument("--gif_encoder", default="pil", choices=["pil", "device"],
                    help="writer of --format gif: pil (per-frame palettes, on the host) or device (one palette for the clip, index map and LZW "
                         "on the device: mmgt_amd.video_out.encode_gif_frames); with --synthetic, device also writes the clip as a .gif")
+    p.add_argument("--gif_dither", default="none", choices=["none", "fs"],
+                   help="with --gif_encoder device: fs = Floyd-Steinberg error diffusion against the clip's palette (smooth gradients stop banding; "
+                        "the file grows)")
+    p.add_argument("--gif_delta", action="store_true",
+                   help="with --gif_encoder device: frame differencing, a pixel that keeps its palette index from one frame to the next is written "
+                        "as the transparent index 255 (a palette of 255 colours)")
     p.add_argument("--decoder", default="pil", choices=["pil", "device"],
                    help="how --pose_path and the mask paths are read: pil = on the host (any input read_frames takes); device = Motion-JPEG "
                         ".avi, a directory of .jpg, of .png or of lossless .webp frames, a .png / .apng file, a .gif file or a lossless .webp file (animated or "
@@ -259,7 +265,8 @@ def run_files(a, dev, dtype):
         shape = list(torch.as_tensor(out.videos).shape)
     else:
         lossy = a.webp_quality if a.format == "webp" else None
-        save_videos_grid(out.videos, path, n_rows=1, fps=a.fps, gif_encoder=a.gif_encoder, webp_quality=lossy)
+        gif = dict(gif_dither=None if a.gif_dither == "none" else a.gif_dither, gif_delta=a.gif_delta) if a.format == "gif" else {}
+        save_videos_grid(out.videos, path, n_rows=1, fps=a.fps, gif_encoder=a.gif_encoder, webp_quality=lossy, **gif)
         if lossy is not None:
             extra = {"webp_quality": lossy}
         shape = list(torch.as_tensor(out.videos).shape)
@@ -342,7 +349,8 @@ def main():
     if a.gif_encoder == "device" and a.format == "gif" and not a.no_decode:
         from mmgt_amd.video_out import save_videos_grid
         extra["gif"] = os.path.splitext(path)[0] + ".gif"
-        save_videos_grid(v, extra["gif"], n_rows=1, fps=a.fps, gif_encoder="device")
+        save_videos_grid(v, extra["gif"], n_rows=1, fps=a.fps, gif_encoder="device", gif_dither=None if a.gif_dither == "none" else a.gif_dither,
+                         gif_delta=a.gif_delta)
         extra["gif_bytes"] = os.path.getsize(extra["gif"])
     if a.format == "apng" and not a.no_decode:
         from mmgt_amd.video_out import save_videos_grid

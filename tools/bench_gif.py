@@ -8,7 +8,10 @@ weights):
     no Clear codes at strip boundaries;
   * end to end on the same box, alternating: save_videos_grid(frames, "x.gif") with gif_encoder="pil" (the default branch, the baseline) against
     gif_encoder="device"; host clock, host uint8 frames in, file out;
-  * file sizes: device, PIL, device with strip_rows = H.
+  * file sizes: device, PIL, device with strip_rows = H;
+  * dithering and frame differencing (encode_gif_frames(dither="fs", delta=True)): ms per frame of the mmgt_gif_dither launch beside
+    mmgt_gif_index; file bytes for the four combinations on the clip and on one with a static background (static_clip); and the share of that
+    background's pixels whose index changes from one frame to the next, with and without dithering: the crawl that eats into what delta saves.
 
     python tools/bench_gif.py [--reps 20] [--pairs 3] [--out profiles/gif/bench_gif.jsonl]"""
 import argparse
@@ -35,6 +38,21 @@ def timed(fn, reps, warm=3):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / reps
+
+
+def static_clip(frames):
+    """A clip with a static background: frame 0 everywhere, and a window of a quarter of each side that shows frame k's own pixels and moves along
+    the diagonal.  -> (the clip, k -> the window's (y0, x0))."""
+    n, H, W, _ = frames.shape
+
+    def box(k):
+        return (k * (H - H // 4)) // max(1, n - 1), (k * (W - W // 4)) // max(1, n - 1)
+
+    clip = frames[:1].repeat(n, 1, 1, 1)
+    for k in range(n):
+        y0, x0 = box(k)
+        clip[k, y0:y0 + H // 4, x0:x0 + W // 4] = frames[k, y0:y0 + H // 4, x0:x0 + W // 4]
+    return clip.contiguous(), box
 
 
 def main():
@@ -106,6 +124,30 @@ def main():
             rec[f"file_bytes_{k}"] = os.path.getsize(path)
             os.remove(path)
         rec["strip_clear_cost"] = round(rec["file_bytes_device"] / rec["file_bytes_device_one_strip"] - 1, 5)
+        # dithering and frame differencing: the dither launch beside mmgt_gif_index, then file bytes for the four combinations on this clip and on
+        # one with a static background, and the crawl of error diffusion over that background (nothing here is gated)
+        pal_d = torch.from_numpy(palette).to(dev)
+        dith = torch.empty_like(idx)
+        scratch = torch.empty((max(4, hip.gif_dither_scratch_bytes(n, H, W)),), device=dev, dtype=torch.uint8)
+        rec["dither_ms_per_frame"] = round(timed(lambda: hip.gif_dither(frames, lut, pal_d, out=dith, scratch=scratch), max(3, a.reps // 4)) / n, 4)
+        rec["dither_band_rows"] = hip.gif_dither_band()
+        still, box = static_clip(frames)
+        for name, clip in (("", frames), ("_static", still)):
+            for dither in (None, "fs"):
+                for delta in (False, True):
+                    pal2, blobs2 = video_out.encode_gif_frames(clip, dither=dither, delta=delta)
+                    path = os.path.join(tmp, "opt.gif")
+                    key = f"file_bytes{name}" + ("_fs" if dither else "") + ("_delta" if delta else "")
+                    rec[key] = video_out.write_gif(path, pal2, blobs2, W, H, 25, transparent=255 if delta else None)
+                    os.remove(path)
+        pal_s = video_out.gif_palette(hip.gif_histogram(still).cpu().numpy().view(np.uint32), 255)
+        lut_s = torch.from_numpy(video_out.gif_lut(pal_s, 255)).to(dev)
+        outside = torch.ones((n - 1, H, W), device=dev, dtype=torch.bool)                     # of frame k + 1: not under the window of frame k or k + 1
+        for k in range(n - 1):
+            for y0, x0 in (box(k), box(k + 1)):
+                outside[k, y0:y0 + H // 4, x0:x0 + W // 4] = False
+        for key, m in (("fs", hip.gif_dither(still, lut_s, torch.from_numpy(pal_s).to(dev))), ("plain", hip.gif_index(still, lut_s))):
+            rec[f"static_region_changed_share_{key}"] = round(float(((m[1:] != m[:-1]) & outside).sum() / outside.sum()), 5)
         print(json.dumps(rec), flush=True)
         lines.append(json.dumps(rec))
     os.rmdir(tmp)
