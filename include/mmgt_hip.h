@@ -297,6 +297,29 @@ int mmgt_sampler_step(const float* pred_sum, const float* counter, const float* 
 int mmgt_cfg_moments(const float* pred_sum, const float* counter, long n, int F, int hw, float guidance, double* partials, int partials_rows,
                      double* moments, void* stream);
 
+/* ---- Re-voicing an existing clip (csrc/vid2vid.hip).
+ * The noised known clip and the kept-region blend.  x0, z, x, out: fp32 [n] = (1, C, F, h, w); mask: fp32 [F * hw], broadcast over C (element i
+ * belongs to frame (i / hw) % F and pixel i % hw).
+ *   known = sa x0 + sb z     one fp32 expression (an fma over the rounded sb z), the same in every use; a zero scalar drops its term, so
+ *                            (sa, sb) = (1, 0) returns x0's bits and (0, 1) z's
+ *   x, mask null:  out = known;   else  out = x where mask == 1, known where mask == 0 (selections), mask x + (1 - mask) known in between.
+ * x and mask come together.  out may alias x, not x0 or z. */
+int mmgt_known_latents(const float* x0, const float* z, const float* x, const float* mask, float* out, long n, int F, int hw, float sa, float sb,
+                       void* stream);
+
+/* Pixel mask uint8 [L][H][W] (H, W multiples of 8) -> latent cell mask fp32 [L][H/8][W/8] of exact 0 / 1: a cell is 1 iff some pixel >= 128 lies
+ * in a cell within Chebyshev distance grow (0 .. 8) of it; cells outside the frame do not exist. */
+int mmgt_mask_to_latent(const unsigned char* mask_px, float* cells, int L, int H, int W, int grow, void* stream);
+
+/* Cell mask fp32 [L][h][w] (a cell counts when >= 0.5) -> paste-back alpha uint8 [L][8h][8w]: the cell mask repeated x 8, box-averaged over
+ * (2r + 1)^2 pixels with edge replication, a = (255 count + area / 2) / area in integers, area = (2r + 1)^2; r = 0 .. 32 (r = 0: 0 / 255).
+ * alpha must be 4-byte aligned. */
+int mmgt_feather_alpha(const float* cells, unsigned char* alpha, int L, int h, int w, int r, void* stream);
+
+/* Paste back: gen, orig, out uint8 [npix][3], alpha uint8 [npix]; every byte (g a + o (255 - a) + 127) / 255 in integer division: a = 0 returns
+ * orig's bytes, a = 255 gen's. */
+int mmgt_composite_u8(const unsigned char* gen, const unsigned char* orig, const unsigned char* alpha, unsigned char* out, long npix, void* stream);
+
 /* pred_sum[:, :, idx[j]] += pred[:, :, j]; counter[idx[j]] += 1 for a window of Fw frames (closed-loop indices).
  * pred is channels-last T ((2*Fw), hw, Cpad) as produced by the UNet; pred_sum fp32 (2, C, F, hw).
  * Replaces: src/pipelines/pipeline_pose2vid_long.py:622-624. */

@@ -96,6 +96,10 @@ _SIGS = {
     "mmgt_sampler_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_float,
                                   c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_void_p]),
     "mmgt_cfg_moments": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p]),
+    "mmgt_known_latents": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_float, c_float, c_void_p]),
+    "mmgt_mask_to_latent": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_feather_alpha": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_composite_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "mmgt_accumulate_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p]),
     "mmgt_rotary": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
@@ -976,6 +980,83 @@ def sampler_step(pred_sum, counter, latents, guidance, sa_t, sb_t, k_x, k_0, k_1
                                    _ptr(noise if k_z != 0.0 else None), _ptr(moments if rescale > 0.0 else None),
                                    _ptr(out), _ptr(x0_out), n, F, hw, guidance, rescale, sa_t, sb_t, k_x, k_0, k_1, k_v, k_z, _stream()),
            "mmgt_sampler_step")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ re-voicing a clip (csrc/vid2vid.hip)
+
+MASK_GROW_MAX, FEATHER_MAX = 8, 32
+
+
+def known_latents(x0, z, sa, sb, x=None, mask=None, out=None):
+    """The noised known clip, and with x / mask the kept-region blend (include/mmgt_hip.h: mmgt_known_latents).  x0, z, x, out: contiguous fp32
+    (1, C, F, h, w); mask: contiguous fp32 (F, h, w), 1 = take x, 0 = take known = sa x0 + sb z.  out may be x.  Every refusal is raised before
+    anything is launched."""
+    _dev(x0, z, x, mask, out)
+    if x0.dim() != 5 or x0.shape[0] != 1:
+        raise RuntimeError(f"known_latents: x0 must be (1, C, F, h, w), got {tuple(x0.shape)}")
+    if (x is None) != (mask is None):
+        raise RuntimeError("known_latents: x and mask come together (the blend needs both, the plain noising neither)")
+    if out is None:
+        out = torch.empty_like(x0)
+    for name, t in (("x0", x0), ("z", z), ("x", x), ("out", out)):
+        if t is not None and (t.shape != x0.shape or t.dtype != torch.float32 or not t.is_contiguous()):
+            raise RuntimeError(f"known_latents: {name} must be contiguous float32 {tuple(x0.shape)}, got {t.dtype} {tuple(t.shape)}")
+    _, C, F, h, w = x0.shape
+    if mask is not None and (tuple(mask.shape) != (F, h, w) or mask.dtype != torch.float32 or not mask.is_contiguous()):
+        raise RuntimeError(f"known_latents: mask must be contiguous float32 {(F, h, w)}, got {mask.dtype} {tuple(mask.shape)}")
+    if out.data_ptr() in (x0.data_ptr(), z.data_ptr()):
+        raise RuntimeError("known_latents: out may be x, not x0 or z")
+    _check(lib().mmgt_known_latents(_ptr(x0), _ptr(z), _ptr(x), _ptr(mask), _ptr(out), x0.numel(), F, h * w, float(sa), float(sb), _stream()),
+           "mmgt_known_latents")
+    return out
+
+
+def mask_to_latent(mask_u8, grow=1):
+    """Pixel mask uint8 (L, H, W), H and W multiples of 8 -> cell mask fp32 (L, H / 8, W / 8) of 0 / 1: 1 iff a pixel >= 128 lies in a cell within
+    Chebyshev distance `grow` (0 .. 8)."""
+    _dev(mask_u8)
+    if mask_u8.dtype != torch.uint8 or mask_u8.dim() != 3 or not mask_u8.is_contiguous():
+        raise RuntimeError(f"mask_to_latent: the mask must be contiguous uint8 (L, H, W), got {mask_u8.dtype} {tuple(mask_u8.shape)}")
+    L, H, W = mask_u8.shape
+    if L < 1 or H < 8 or W < 8 or H % 8 or W % 8:
+        raise RuntimeError(f"mask_to_latent: H and W must be multiples of 8 (the VAE's cell), got {H} x {W}")
+    if int(grow) != grow or not 0 <= grow <= MASK_GROW_MAX:
+        raise RuntimeError(f"mask_to_latent: grow must be an integer in 0 .. {MASK_GROW_MAX}, got {grow}")
+    out = torch.empty((L, H // 8, W // 8), device=mask_u8.device, dtype=torch.float32)
+    _check(lib().mmgt_mask_to_latent(_ptr(mask_u8), _ptr(out), L, H, W, int(grow), _stream()), "mmgt_mask_to_latent")
+    return out
+
+
+def feather_alpha(cells, r=8):
+    """Cell mask fp32 (L, h, w) -> paste-back alpha uint8 (L, 8 h, 8 w): the mask repeated x 8 and box-averaged over (2 r + 1)^2 pixels with edge
+    replication, in integers (include/mmgt_hip.h: mmgt_feather_alpha); r in 0 .. 32."""
+    _dev(cells)
+    if cells.dtype != torch.float32 or cells.dim() != 3 or not cells.is_contiguous() or cells.numel() == 0:
+        raise RuntimeError(f"feather_alpha: the cell mask must be contiguous float32 (L, h, w), got {cells.dtype} {tuple(cells.shape)}")
+    if int(r) != r or not 0 <= r <= FEATHER_MAX:
+        raise RuntimeError(f"feather_alpha: the radius must be an integer in 0 .. {FEATHER_MAX}, got {r}")
+    L, h, w = cells.shape
+    out = torch.empty((L, 8 * h, 8 * w), device=cells.device, dtype=torch.uint8)
+    _check(lib().mmgt_feather_alpha(_ptr(cells), _ptr(out), L, h, w, int(r), _stream()), "mmgt_feather_alpha")
+    return out
+
+
+def composite_u8(gen, orig, alpha, out=None):
+    """gen, orig uint8 (L, H, W, 3), alpha uint8 (L, H, W) -> uint8 (L, H, W, 3): every byte (g a + o (255 - a) + 127) / 255."""
+    _dev(gen, orig, alpha, out)
+    if gen.dtype != torch.uint8 or gen.dim() != 4 or gen.shape[3] != 3 or not gen.is_contiguous() or gen.numel() == 0:
+        raise RuntimeError(f"composite_u8: gen must be contiguous uint8 (L, H, W, 3), got {gen.dtype} {tuple(gen.shape)}")
+    if out is None:
+        out = torch.empty_like(gen)
+    for name, t in (("orig", orig), ("out", out)):
+        if t.dtype != torch.uint8 or t.shape != gen.shape or not t.is_contiguous():
+            raise RuntimeError(f"composite_u8: {name} must be contiguous uint8 {tuple(gen.shape)} like gen, got {t.dtype} {tuple(t.shape)}")
+    if alpha.dtype != torch.uint8 or tuple(alpha.shape) != tuple(gen.shape[:3]) or not alpha.is_contiguous():
+        raise RuntimeError(f"composite_u8: alpha must be contiguous uint8 {tuple(gen.shape[:3])}, got {alpha.dtype} {tuple(alpha.shape)}")
+    if out.data_ptr() in (gen.data_ptr(), orig.data_ptr(), alpha.data_ptr()):
+        raise RuntimeError("composite_u8: out must be a buffer of its own")
+    _check(lib().mmgt_composite_u8(_ptr(gen), _ptr(orig), _ptr(alpha), _ptr(out), alpha.numel(), _stream()), "mmgt_composite_u8")
     return out
 
 

@@ -17,6 +17,9 @@ device (mmgt_amd/conditioning.py) instead of cv2 / PIL on the host.
   resize_frames_device / ref_image_tensors_device
                      PIL's Image.resize (bilinear / bicubic / Lanczos) on device frames, and the reference image's two prologue inputs
                      (the VAE's Lanczos-resized [-1, 1] tensor, CLIP's bicubic 224 x 224 normalised pixel values) from a device image
+  add_revoice_arguments / revoice_kwargs
+                     the scripts' flags of re-voicing an existing clip (--init_video, --strength, --regen_mask, --mask_grow, --paste_back,
+                     --feather) and the pipeline arguments they become
   load_checkpoint    a state dict from .safetensors / .pth / .pt / .bin / .ckpt or a diffusers-style directory
   split_net_checkpoint   the reference's `Net` checkpoint (net-<num_c>.pth, scripts/pose2vid.py:41-67,186-190) -> per-module dicts
 """
@@ -211,6 +214,63 @@ def motion_masks_device(face_u8: torch.Tensor, lips_u8: torch.Tensor, hands_u8: 
     lips = pyramid(lips_u8, 21, "lips")
     hands = pyramid(hands_u8, 21, "hands") if hands_u8 is not None else [torch.zeros_like(m) for m in lips]
     return C.full_mask_with_hands(face, lips, hands), face, lips
+
+
+def add_revoice_arguments(p):
+    """The flags of re-voicing an existing clip, shared by scripts/pose2vid.py and scripts/audio2vid.py."""
+    p.add_argument("--init_video", type=str, default=None,
+                   help="an existing clip to re-voice instead of sampling from noise: anything read_frames reads (a directory of images, .npy, "
+                        "Motion-JPEG .avi, .apng, .gif, .webp); frames of another size are Lanczos-resized on the device")
+    p.add_argument("--strength", type=float, default=1.0,
+                   help="with --init_video: the part of the schedule that is run, in (0, 1]: the last int(steps * strength) steps")
+    p.add_argument("--regen_mask", type=str, default=None,
+                   help="with --init_video: the region that is re-synthesised -- face, lips or full (face + lips + hands) of the run's own mask "
+                        "clips, or the path of a mask clip (>= 128 = regenerate); the rest of the clip is kept")
+    p.add_argument("--mask_grow", type=int, default=1, help="latent cells (8 x 8 pixels) by which --regen_mask is dilated, 0 .. 8")
+    p.add_argument("--paste_back", action="store_true",
+                   help="with --init_video: composite the decoded frames onto the clip's own frames outside the (feathered) mask, on the device")
+    p.add_argument("--feather", type=int, default=8, help="radius in pixels of the box blur of --paste_back's alpha, 0 .. 32")
+
+
+def frames_tensor_u8(frames: Sequence) -> torch.Tensor:
+    """PIL frames of one size -> (L, h, w, 3) uint8 RGB"""
+    arrs = [np.asarray(f.convert("RGB"), dtype=np.uint8) for f in frames]
+    if len({a.shape for a in arrs}) != 1:
+        raise RuntimeError(f"the frames of a clip must have one size, got {sorted({a.shape[:2] for a in arrs})}")
+    return torch.from_numpy(np.stack(arrs))
+
+
+def revoice_kwargs(a, masks: Dict[str, Optional[torch.Tensor]], length: int, device, on_device: bool = False, **decode_kw) -> dict:
+    """The pipeline's init arguments from the flags of `add_revoice_arguments`.  masks: {"face", "lips", "hands"} -> (L, h, w) uint8 pixel masks
+    (tensor or None) of the run's own mask clips, for --regen_mask face / lips / full.  The clip is read on the device when on_device and its
+    container is one read_frames_device takes (everything but .npy); the flags without --init_video are handed on, and the pipeline refuses them."""
+    kw = {}
+    if a.strength != 1.0:
+        kw["strength"] = a.strength
+    if a.paste_back:
+        kw["paste_back"] = True
+    if a.init_video:
+        if on_device and not str(a.init_video).lower().endswith(".npy"):
+            from .video_in import read_frames_device
+            clip = read_frames_device(a.init_video, length, device, **decode_kw)
+        else:
+            clip = frames_tensor_u8(read_frames(a.init_video, length)).to(device)
+        if clip.shape[0] < length:
+            raise SystemExit(f"--init_video {a.init_video} has {clip.shape[0]} frames, the run samples {length}")
+        kw.update(init_video=clip[:length].contiguous(), mask_grow=a.mask_grow, feather=a.feather)
+    if a.regen_mask:
+        if a.regen_mask in ("face", "lips", "full"):
+            names = ("face", "lips", "hands") if a.regen_mask == "full" else (a.regen_mask,)
+            parts = [masks[n][:length].to(device) for n in names if masks.get(n) is not None]
+            if not parts or len({tuple(p.shape) for p in parts}) != 1:
+                raise SystemExit(f"--regen_mask {a.regen_mask}: the run's mask clips are missing or differ in size")
+            m = parts[0]
+            for q in parts[1:]:
+                m = torch.maximum(m, q)
+        else:
+            m = _mask_stack(read_frames(a.regen_mask, length), length).to(device)
+        kw["regen_mask"] = m.contiguous()
+    return kw
 
 
 def load_checkpoint(path) -> Dict[str, torch.Tensor]:

@@ -13,6 +13,9 @@ is None), `decode=False`, `window_group=` / `cfg_split=` (window-parallel sampli
 `DPMSolverMultistepScheduler` as `scheduler` select the update behind the accumulation (see `denoise`); the defaults are the reference's DDIM.
 `ref_image` may be a uint8 (h, w, 3) RGB tensor instead of a PIL image: the Lanczos resize in front of the VAE and the bicubic 224 x 224 resize
 in front of CLIP then run on the device (mmgt_amd.inputs.ref_image_tensors_device), with PIL's bytes.
+`init_video=` / `init_latents=`, `strength=`, `regen_mask=`, `mask_grow=`, `paste_back=`, `feather=` re-voice an existing clip instead of sampling
+from noise: the clip is noised to the start of the last int(N strength) steps, the cells outside the mask are put back after every
+step, and the decoded frames can be composited onto the clip's own frames on the device.
 `output_type="uint8"` returns the frames as uint8 (b, f, H, W, 3), converted on the device (what save_videos_grid writes).
 `output_type="jpeg"` (with `jpeg_quality=`, `jpeg_subsampling=`) returns one JPEG file (bytes) per frame, encoded on the device.
 """
@@ -159,11 +162,76 @@ class Pose2VideoPipeline:
                              f"guidance_rescale={guidance_rescale}")
         return dpm
 
+    @staticmethod
+    def _check_init_args(init_video, init_latents, strength, regen_mask, paste_back, video_length, window_group, num_images_per_prompt,
+                         interpolation_factor, output_type):
+        """The refusals of re-voicing's arguments (each names both parties) -> whether an init clip was given."""
+        given = [n for n, v in (("init_video", init_video), ("init_latents", init_latents)) if v is not None]
+        if len(given) == 2:
+            raise ValueError("init_video and init_latents are two forms of the same clip: pass exactly one of them")
+        if not given:
+            for name, on in ((f"strength={strength}", float(strength) != 1.0), ("regen_mask", regen_mask is not None), ("paste_back", bool(paste_back))):
+                if on:
+                    raise ValueError(f"{name} changes how an existing clip is re-sampled: it needs init_video or init_latents")
+            return False
+        init = given[0]
+        if window_group is not None:
+            raise ValueError(f"{init} is not combined with window_group (re-voicing was never run on more than one rank): use one GPU")
+        if num_images_per_prompt > 1:
+            raise ValueError(f"{init} is not combined with num_images_per_prompt={num_images_per_prompt}: one init clip gives one clip")
+        if interpolation_factor > 1:
+            raise ValueError(f"{init} is not combined with interpolation_factor={interpolation_factor}: the interpolated frames have no "
+                             "counterpart in the init clip")
+        clip = init_video if init_video is not None else init_latents
+        n = clip.shape[0] if init_video is not None else (clip.shape[2] if clip.dim() == 5 else -1)
+        if n != video_length:
+            raise ValueError(f"{init} has {n} frames (shape {tuple(clip.shape)}), video_length={video_length}: the init clip must have the "
+                             "sampled clip's length")
+        if paste_back and init_video is None:
+            raise ValueError("paste_back composites the decoded frames onto the init clip's frames: it needs init_video, not init_latents")
+        if paste_back and output_type != "uint8":
+            raise ValueError(f'paste_back composites uint8 frames on the device: it needs output_type="uint8", got output_type={output_type!r}')
+        return True
+
+    def _init_clip(self, init_video, init_latents, regen_mask, mask_grow, z, width, height, dev):
+        """-> (x0 (1, 4, L, h, w) fp32, cell mask (L, h, w) fp32 or None, the init frames at width x height or None), all on the device."""
+        from .inputs import resize_frames_device
+        frames = None
+        if init_video is not None:
+            frames = torch.as_tensor(init_video).to(dev)
+            if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+                raise ValueError(f"init_video: expected uint8 (L, h, w, 3) frames, got {frames.dtype} {tuple(frames.shape)}")
+            if tuple(frames.shape[1:3]) != (height, width):
+                frames = resize_frames_device(frames, width, height, "lanczos")        # as the reference image (DESIGN 4f)
+            frames = frames.contiguous()
+            if not hasattr(self.vae, "encode_video"):
+                raise RuntimeError("init_video needs a VAE with an encoder (AutoencoderKL.encode_video): pass init_latents=(1, 4, L, h, w)")
+            x0 = self.vae.encode_video(frames)
+        else:
+            x0 = init_latents.to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(x0.shape) != tuple(z.shape):
+            raise ValueError(f"the init clip's latents are {tuple(x0.shape)}, the sampler's {tuple(z.shape)}")
+        cells = None
+        if regen_mask is not None:
+            m = torch.as_tensor(regen_mask).to(dev)
+            L, h, w = z.shape[2:]
+            if m.dim() != 3 or m.shape[0] != L:
+                raise ValueError(f"regen_mask must be (L, H, W) uint8 pixels or (L, h, w) float32 cells with L = {L}, got {tuple(m.shape)}")
+            if m.dtype == torch.uint8:
+                if tuple(m.shape[1:]) != (height, width):
+                    m = resize_frames_device(m[..., None].contiguous(), width, height, "bilinear")[..., 0]
+                cells = hip.mask_to_latent(m.contiguous(), mask_grow)
+            elif m.dtype == torch.float32 and tuple(m.shape) == (L, h, w):
+                cells = m.contiguous()
+            else:
+                raise ValueError(f"regen_mask must be uint8 (L, H, W) pixels or float32 {(L, h, w)} cells, got {m.dtype} {tuple(m.shape)}")
+        return x0, cells, frames
+
     # --------------------------------------------------------------------------------------------- the hot loop
     def denoise(self, latents, timesteps, encoder_hidden_states, pose_fea, audio_tensor_pre, full_masks, face_masks,
                 lip_masks, guidance_scale, motion_scale, context_frames, context_stride, context_overlap,
                 context_schedule="uniform", num_inference_steps=None, callback=None, callback_steps=1,
-                window_group=None, cfg_split="auto", context_batch_size=1, eta=0.0, guidance_rescale=0.0, generator=None):
+                window_group=None, cfg_split="auto", context_batch_size=1, eta=0.0, guidance_rescale=0.0, generator=None, known=None):
         """pipeline_pose2vid_long.py:494-643.  latents (1, C, L, h, w) fp32 on the GPU; returns the final latents.
 
         window_group: a torch.distributed process group (or True for the default group) turns on window-parallel sampling of
@@ -185,7 +253,13 @@ class Pose2VideoPipeline:
         hip.cfg_ddim_step, as ever.  Anything else is hip.sampler_step: eta > 0 draws one fp32 noise tensor per step from `generator` (after the
         initial latents, in step order); guidance_rescale > 0 scales the guided prediction to the conditional one's standard deviation (the
         moments stay on the device); a DPMSolverMultistepScheduler hands every step's x0 to the next through two buffers allocated here.  All of
-        it runs after the gather, so it combines with window_group and context_batch_size -- except eta > 0 with window_group."""
+        it runs after the gather, so it combines with window_group and context_batch_size -- except eta > 0 with window_group.
+
+        known = (x0, z, mask) keeps a region of an existing clip: after every step's update -- whichever of the above it is -- one
+        hip.known_latents launch replaces the cells where the fp32 (L, h, w) mask is 0 by sa x0 + sb z at scheduler.alpha_bar_after(t), in
+        place; the callback sees the latents after it.  Behind the last step alpha-bar is 1 and those cells are x0's bits."""
+        if known is not None and window_group is not None:
+            raise ValueError("known= (the kept region of an init clip) is not combined with window_group: use one GPU")
         eta, guidance_rescale = float(eta), float(guidance_rescale)
         dpm = self._check_update_args(eta, guidance_rescale, window_group)
         general = dpm or eta != 0.0 or guidance_rescale != 0.0
@@ -333,6 +407,9 @@ class Pose2VideoPipeline:
                 latents = hip.sampler_step(pred_sum, counter, latents, float(guidance_scale), *self.scheduler.update_coefficients(t, eta),
                                            rescale=guidance_rescale, noise=noise, prev_x0=x0_bufs[(i - 1) % 2] if dpm and i > 0 else None,
                                            x0_out=x0_bufs[i % 2] if dpm else None)
+            if known is not None:
+                from .scheduler import known_scalars
+                hip.known_latents(known[0], known[1], *known_scalars(self.scheduler.alpha_bar_after(t)), x=latents, mask=known[2], out=latents)
             if callback is not None and i % callback_steps == 0:
                 callback(i, t, latents)
         return latents
@@ -351,9 +428,16 @@ class Pose2VideoPipeline:
             raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
         if not guidance_scale > 1.0:
             raise NotImplementedError("classifier-free guidance is mandatory in the reference loop (App. C-7)")
+        init_video, init_latents, regen_mask = kwargs.get("init_video"), kwargs.get("init_latents"), kwargs.get("regen_mask")
+        strength, paste_back = float(kwargs.get("strength", 1.0)), bool(kwargs.get("paste_back", False))
+        revoice = self._check_init_args(init_video, init_latents, strength, regen_mask, paste_back, video_length, kwargs.get("window_group"),
+                                        num_images_per_prompt, interpolation_factor, output_type)
         unet = self.denoising_unet
         dev = unet.device
-        self.scheduler.set_timesteps(num_inference_steps, device=None)
+        if revoice:                                              # the last int(N strength) steps of the same schedule
+            self.scheduler.set_timesteps(num_inference_steps, device=None, strength=strength)
+        else:
+            self.scheduler.set_timesteps(num_inference_steps, device=None)
         timesteps = self.scheduler.timesteps
 
         # ---- prologue (once per clip) -------------------------------------------------------------------
@@ -393,6 +477,15 @@ class Pose2VideoPipeline:
 
         latents = self.prepare_latents(num_images_per_prompt, unet.in_channels, width, height, video_length,
                                        torch.float32, dev, generator, latents=kwargs.get("latents"))
+        known = cells = init_frames = None
+        if revoice:
+            # the noise is the tensor just drawn (init_noise_sigma is 1 on this schedule): no further generator draw.  The start is the init clip
+            # noised to timesteps[0]'s alpha-bar; at strength 1 that alpha-bar is exactly 0 (zero terminal SNR) and the start is z's bits
+            from .scheduler import known_scalars
+            x0, cells, init_frames = self._init_clip(init_video, init_latents, regen_mask, kwargs.get("mask_grow", 1), latents, width, height, dev)
+            z = latents
+            latents = hip.known_latents(x0, z, *known_scalars(self.scheduler._alpha_bar(int(timesteps[0]))))
+            known = (x0, z, cells) if cells is not None else None
 
         pose_fea = kwargs.get("pose_features")
         if pose_fea is None:
@@ -414,7 +507,7 @@ class Pose2VideoPipeline:
                                context_schedule, num_inference_steps, callback, callback_steps,
                                window_group=kwargs.get("window_group"), cfg_split=kwargs.get("cfg_split", "auto"),
                                context_batch_size=context_batch_size, eta=eta, guidance_rescale=guidance_rescale,
-                               generator=generator if isinstance(generator, torch.Generator) else None)
+                               generator=generator if isinstance(generator, torch.Generator) else None, **({"known": known} if known else {}))
         unet.clear_banks()                                                                # :645-646
 
         if interpolation_factor > 0:
@@ -425,7 +518,18 @@ class Pose2VideoPipeline:
             images = self.decode_latents_jpeg(latents, kwargs.get("window_group"), kwargs.get("jpeg_quality", 90),
                                               kwargs.get("jpeg_subsampling", "4:2:0"))
             return Pose2VideoPipelineOutput(videos=images) if return_dict else images
-        images = self.decode_latents(latents, kwargs.get("window_group"), uint8=output_type == "uint8")
+        if paste_back:
+            # the decoded frames over the init clip's, on the device: alpha is the feathered cell mask (255 everywhere without a mask, where the
+            # composite is the decoded frames themselves and is not launched)
+            if self.vae is None:
+                raise RuntimeError("decode_latents needs a VAE (pass decode=False to get latents)")
+            frames = self.vae.decode_video_uint8(latents)                                 # (1, L, H, W, 3)
+            if cells is not None:
+                alpha = hip.feather_alpha(cells, kwargs.get("feather", 8))
+                frames = hip.composite_u8(frames[0].contiguous(), init_frames, alpha)[None]
+            images = frames.cpu().numpy()
+        else:
+            images = self.decode_latents(latents, kwargs.get("window_group"), uint8=output_type == "uint8")
         if output_type in ("tensor", "uint8"):
             images = torch.from_numpy(images)
         if not return_dict:

@@ -10,6 +10,10 @@ class name but has not been compared with diffusers.  Both classes give `update_
 mmgt_sampler_step evaluates,
 
     x0 = sa_t x - sb_t v;    x_next = k_x x + k_0 x0 + k_1 x0_prev + k_v v + k_z z.
+
+Re-voicing an existing clip: `set_timesteps(N, strength=)` keeps the last int(N strength) steps of the trailing list (diffusers' img2img
+`get_timesteps`), `alpha_bar_after(t)` is where the step leaving t lands, and `known_scalars(alpha_bar)` are the two scalars of mmgt_known_latents
+that noise the known clip to that level.
 """
 import math
 
@@ -48,15 +52,32 @@ class DDIMScheduler:
         self.num_inference_steps = None
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy().astype(np.int64))
 
-    def set_timesteps(self, num_inference_steps, device=None):
+    def set_timesteps(self, num_inference_steps, device=None, strength=1.0):
+        """strength < 1 keeps the LAST min(int(N strength), N) entries of the trailing list (diffusers' img2img `get_timesteps`, its float
+        truncation included): the steps a clip noised to timesteps[0] still has to take.  num_inference_steps stays N, so the kept steps are
+        the ones the full schedule takes."""
         if num_inference_steps > self.num_train_timesteps:
             raise ValueError("num_inference_steps exceeds num_train_timesteps")
+        if not 0.0 <= strength <= 1.0:
+            raise ValueError(f"strength must lie in [0, 1], got strength={strength}")
+        keep = min(int(num_inference_steps * strength), num_inference_steps)
+        if keep < 1:
+            raise ValueError(f"num_inference_steps={num_inference_steps} at strength={strength} leaves no step to take "
+                             f"(int({num_inference_steps} * {strength}) = 0)")
         self.num_inference_steps = num_inference_steps
         ratio = self.num_train_timesteps / num_inference_steps
         ts = np.round(np.arange(self.num_train_timesteps, 0, -ratio)).astype(np.int64) - 1
-        self.timesteps = torch.from_numpy(ts)
+        self.timesteps = torch.from_numpy(ts[max(num_inference_steps - keep, 0):].copy())
         if device is not None:
             self.timesteps = self.timesteps.to(device)
+
+    def alpha_bar_after(self, timestep):
+        """the alpha-bar on which the step leaving `timestep` lands (fp64 Python float): alphas_cumprod[t - 1000 // N]; behind the last entry of
+        self.timesteps final_alpha_cumprod.  (Where 1000 // N divides the last timestep -- N = 6: 166 - 166 = 0 -- the update itself lands on
+        alphas_cumprod[0] = 0.9991, the reference's quirk; what is kept of a known clip ends as the clip, not with 3 % of noise on it.)"""
+        if int(timestep) == int(self.timesteps[-1]):
+            return float(self.final_alpha_cumprod)
+        return self._alpha_bar(int(timestep) - self.num_train_timesteps // self.num_inference_steps)
 
     def scale_model_input(self, sample, timestep=None):
         return sample
@@ -85,6 +106,12 @@ class DDIMScheduler:
 
 def _f32_tuple(vals):
     return tuple(float(np.float32(v)) for v in vals)
+
+
+def known_scalars(alpha_bar):
+    """(sqrt(abar), sqrt(1 - abar)) as fp32-rounded Python floats: the scalars of hip.known_latents that noise a known clip to `alpha_bar`.
+    abar = 0 gives exactly (0, 1) and abar = 1 exactly (1, 0), so the ends of the schedule are z's and x0's bits."""
+    return _f32_tuple((math.sqrt(alpha_bar), math.sqrt(1 - alpha_bar)))
 
 
 def ddim_coefficients(a_t, a_s, eta):
@@ -134,6 +161,12 @@ class DPMSolverMultistepScheduler(DDIMScheduler):
         i = ts.index(int(timestep))
         a_prev = self._alpha_bar(ts[i - 1]) if i > 0 else None
         return dpmpp2m_coefficients(a_prev, self._alpha_bar(ts[i]), self._alpha_bar(ts[i + 1] if i + 1 < len(ts) else -1))
+
+    def alpha_bar_after(self, timestep):
+        """the alpha-bar of the next entry of self.timesteps, final_alpha_cumprod behind the last"""
+        ts = [int(t) for t in self.timesteps]
+        i = ts.index(int(timestep))
+        return self._alpha_bar(ts[i + 1] if i + 1 < len(ts) else -1)
 
     def update_coefficients(self, timestep, eta=0.0):
         """(sa_t, sb_t, k_x, k_0, k_1, k_v, k_z) as fp32-rounded Python floats; k_1 != 0 marks a second-order step, which reads the x0 of the

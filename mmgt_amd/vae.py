@@ -334,6 +334,29 @@ class AutoencoderKL:
         out = hip.nhwc_to_ncfhw(mom, 1, 4)                                                       # (1, 4, n, h, w)
         return out[0].permute(1, 0, 2, 3).contiguous()
 
+    def encode_video(self, frames_u8, frames_per_batch=8):
+        """A clip's latents on the device: uint8 (L, H, W, 3) frames there -> fp32 (1, 4, L, H / 8, W / 8) =
+        `vae.encode(frame).latent_dist.mean * 0.18215` of every frame.  The float stage is the reference image's own table, v / 255 * 2 - 1 with
+        pipeline._pil_to_tensor's operations as 256 entries (inputs.ref_image_tensors_device); the frames pass the encoder in chunks."""
+        import numpy as np
+        from . import conditioning as C
+        x = frames_u8
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[3] != 3 or not x.is_cuda:
+            raise ValueError(f"encode_video: expected uint8 (L, H, W, 3) frames on the device, got {getattr(x, 'dtype', type(x))} "
+                             f"{tuple(getattr(x, 'shape', ()))}")
+        if not self._has_encoder:
+            raise RuntimeError("AutoencoderKL.encode: the encoder weights were not loaded")
+        L, H, W, _ = x.shape
+        if L < 1 or H % 8 or W % 8:
+            raise ValueError(f"encode_video: the frames must be a multiple of 8 in both directions, got {L} frames of {W} x {H}")
+        lut = (torch.from_numpy(np.arange(256).astype(np.float32) / 255.0) * 2.0 - 1.0).repeat(3, 1).to(x.device)
+        outs = []
+        for f0 in range(0, L, int(frames_per_batch)):
+            planar = C.resize_u8_device(x[f0:f0 + int(frames_per_batch)].contiguous(), H, W, "lanczos", lut=lut)      # (3, n, H, W): the size stays
+            img = hip.ncfhw_to_nhwc(planar[None].contiguous(), 64, self._dtype)                                     # frames as the f axis
+            outs.append(hip.nhwc_to_ncfhw(self.encode_nhwc(img), 1, 4, scale=0.18215))
+        return torch.cat(outs, dim=2)
+
     def decode(self, z):
         """diffusers-style: z (n, 4, h, w) -> DecoderOutput(sample (n, 3, 8h, 8w))."""
         zz = z.to(self._device, torch.float32).contiguous()[:, :, None]                         # (n, 4, 1, h, w)

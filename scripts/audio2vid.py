@@ -3,6 +3,7 @@
 "SMGA audio2pose + Stage-2 denoise".
 
     python scripts/audio2vid.py --synthetic -W 512 -H 512 -L 24 --steps 25
+    python scripts/audio2vid.py --synthetic -L 24 --init_video clip.npy --regen_mask lips --paste_back    # dub an existing clip
 
 The chain is the reference's (line numbers of its scripts/audio2vid.py):
   1. Stage-1 SMGA (:198-200,324-348): one guided 50-step DDIM sample of 80 key-point frames per 3.2-second audio slice, each slice
@@ -94,6 +95,8 @@ def parse_args():
     p.add_argument("--eta", type=float, default=0.0, help="DDIM's stochasticity (0 = deterministic, 1 = ancestral); not with --sampler dpmpp2m")
     p.add_argument("--guidance_rescale", type=float, default=0.0,
                    help="in [0, 1]: rescale the guided prediction to the conditional one's standard deviation (Lin et al. 2305.08891, 3.4)")
+    from mmgt_amd.inputs import add_revoice_arguments
+    add_revoice_arguments(p)
     return p.parse_args()
 
 
@@ -277,10 +280,13 @@ def main():
         ref_img = Image.open(a.image_path).convert("RGB")
     elif ref_img is None:
         ref_img = Image.fromarray(((hash_uniform("a2v.ref", (a.H, a.W, 3), 0.5) + 0.5) * 255).clamp(0, 255).to(torch.uint8).numpy())
+    # --init_video and its flags: the drawn 512 x 512 mask frames are the pixel masks (the pipeline resizes them to W x H)
+    from mmgt_amd.inputs import revoice_kwargs
+    revoice = revoice_kwargs(a, {"face": face_u8, "lips": lips_u8, "hands": _hands_u8}, a.L, dev)
     t0 = time.time()
     out = pipe(ref_img, pose, audio_tensor.float(), full, face, lips, a.W, a.H, a.L, a.steps, a.cfg,
                generator=torch.manual_seed(a.seed), motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c,
-               context_batch_size=a.context_batch_size, output_type="uint8", eta=a.eta, guidance_rescale=a.guidance_rescale)
+               context_batch_size=a.context_batch_size, output_type="uint8", eta=a.eta, guidance_rescale=a.guidance_rescale, **revoice)
     torch.cuda.synchronize()
     timing["stage2_s"] = round(time.time() - t0, 3)
     v = torch.as_tensor(out.videos)                                                                          # (1, L, H, W, 3) uint8
@@ -305,7 +311,8 @@ def main():
             extra["webp_quality"] = lossy
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
                       "dtype": a.dtype, "context_batch_size": a.context_batch_size, "sampler": a.sampler, "eta": a.eta,
-                      "guidance_rescale": a.guidance_rescale, "keypoints_finite": bool(np.isfinite(kps).all()),
+                      "guidance_rescale": a.guidance_rescale, "init_video": a.init_video, "strength": a.strength, "regen_mask": a.regen_mask,
+                      "paste_back": a.paste_back, "keypoints_finite": bool(np.isfinite(kps).all()),
                       "mask_levels": [list(m.shape) for m in face], **timing, **extra}))
 
 

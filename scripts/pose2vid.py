@@ -4,6 +4,7 @@
     python scripts/pose2vid.py --synthetic -W 512 -H 512 -L 24 --steps 25         # BASELINE config 2 geometry
     python scripts/pose2vid.py --synthetic -W 64 -H 64 -L 8 --steps 4             # config 1 geometry
     python scripts/pose2vid.py --synthetic --sampler dpmpp2m --steps 12 --guidance_rescale 0.7    # DPM-Solver++ 2M; --eta with ddim
+    python scripts/pose2vid.py --synthetic --init_video clip.npy --strength 0.5 --regen_mask lips --paste_back    # re-voice an existing clip
 
     python scripts/pose2vid.py --image_path ref.png --pose_path pose_frames/ --face_mask_path face.npy --lips_mask_path lips.npy \
         [--hands_mask_path hands/] -c configs/prompts/animation.yaml          # the reference's single-sample mode (:196-300)
@@ -100,6 +101,8 @@ def parse_args():
     p.add_argument("--eta", type=float, default=0.0, help="DDIM's stochasticity (0 = deterministic, 1 = ancestral); not with --sampler dpmpp2m")
     p.add_argument("--guidance_rescale", type=float, default=0.0,
                    help="in [0, 1]: rescale the guided prediction to the conditional one's standard deviation (Lin et al. 2305.08891, 3.4)")
+    from mmgt_amd.inputs import add_revoice_arguments
+    add_revoice_arguments(p)
     return p.parse_args()
 
 
@@ -206,6 +209,16 @@ def load_inputs(a, dev):
     return pose, full, face, lips, L
 
 
+def mask_clips(a, dev, L):
+    """The run's own mask clips as (L, h, w) uint8 pixel masks, for --regen_mask face / lips / full (read again: `load_inputs` keeps only the
+    blurred pyramids)."""
+    from mmgt_amd import inputs
+    if a.regen_mask not in ("face", "lips", "full"):
+        return {}
+    paths = {"face": a.face_mask_path, "lips": a.lips_mask_path, "hands": a.hands_mask_path if a.hands_mask_path and os.path.exists(a.hands_mask_path) else None}
+    return {k: inputs._mask_stack(inputs.read_frames(v, L), L) if v else None for k, v in paths.items()}
+
+
 def load_ref_image(a, dev):
     """The reference image as the pipeline takes it: a PIL image, or with --decoder device a uint8 (h, w, 3) tensor on the device -- a baseline
     .jpg (with --decode_progressive_jpeg: a progressive one too), a .png or a lossless .webp (its first frame) is decoded there, any other file is opened by PIL and its bytes uploaded -- whose resizes then run on the device too."""
@@ -243,12 +256,17 @@ def run_files(a, dev, dtype):
     ref_img = load_ref_image(a, dev)
     pose, full, face, lips, L = load_inputs(a, dev)
     audio = torch.zeros(1, L, 32, 768)                        # pose2vid runs with null audio (:279)
+    from mmgt_amd.inputs import revoice_kwargs
+    lossy = {"webp_lossy": True} if a.decode_lossy_webp else {}
+    if a.decode_progressive_jpeg:
+        lossy["jpeg_progressive"] = True
+    revoice = revoice_kwargs(a, mask_clips(a, dev, L), L, dev, a.decoder == "device", **lossy)       # --init_video and its flags
     gen = torch.manual_seed(a.seed)
     torch.cuda.synchronize()
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, L, a.steps, a.cfg, generator=gen, motion_scale=[1.0, 1.0, 2.0],
                context_frames=a.num_c, context_batch_size=a.context_batch_size, output_type="jpeg" if a.format == "avi" else "uint8",
-               jpeg_quality=a.quality, eta=a.eta, guidance_rescale=a.guidance_rescale)
+               jpeg_quality=a.quality, eta=a.eta, guidance_rescale=a.guidance_rescale, **revoice)
     torch.cuda.synchronize()
     dt = time.time() - t0
     save_dir = os.path.join(a.out_dir, f"multi_person_{a.num_c}")
@@ -273,7 +291,7 @@ def run_files(a, dev, dtype):
     print(json.dumps({"video": shape, "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype,
                       "context_batch_size": a.context_batch_size, "sampler": a.sampler, "eta": a.eta, "guidance_rescale": a.guidance_rescale,
-                      **extra}))
+                      "init_video": a.init_video, "strength": a.strength, "regen_mask": a.regen_mask, "paste_back": a.paste_back, **extra}))
 
 
 def main():
@@ -318,13 +336,17 @@ def main():
     audio = torch.zeros(1, a.L, 32, 768)                      # pose2vid runs with null audio (:279)
     from PIL import Image
     ref_img = Image.fromarray(((hash_uniform("p2v.ref", (a.H, a.W, 3), 0.5) + 0.5) * 255).clamp(0, 255).to(torch.uint8).numpy())
+    # --init_video and its flags: the synthetic masks' first level is the latent grid itself, so a cell >= 0.5 is 8 x 8 pixels of 255
+    from mmgt_amd.inputs import revoice_kwargs
+    cell_px = lambda lv: (lv[0].view(a.L, lat, lat) >= 0.5).to(torch.uint8).mul(255).repeat_interleave(8, 1).repeat_interleave(8, 2)
+    revoice = revoice_kwargs(a, {"face": cell_px(face), "lips": cell_px(lips), "hands": cell_px(hands) if a.hands_mask_path else None}, a.L, dev)
     torch.cuda.synchronize()
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, a.L, a.steps, a.cfg, generator=gen,
                motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c, context_batch_size=a.context_batch_size,
-               output_type="uint8" if a.clip_parallel else "tensor",
+               output_type="uint8" if a.clip_parallel or a.paste_back else "tensor",
                decode=not a.no_decode,                         # CLIP embedding and ref_image_latents: HIP encoders, from ref_img
-               window_group=True if a.window_parallel else None, eta=a.eta, guidance_rescale=a.guidance_rescale)
+               window_group=True if a.window_parallel else None, eta=a.eta, guidance_rescale=a.guidance_rescale, **revoice)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if a.clip_parallel:
@@ -373,6 +395,7 @@ def main():
                       "steps": a.steps, "windows_per_step": len(list(__import__("mmgt_amd.context", fromlist=["uniform"]).uniform(
                           0, a.steps, a.L, a.num_c, 1, 4))), "context_batch_size": a.context_batch_size, "dtype": a.dtype,
                       "sampler": a.sampler, "eta": a.eta, "guidance_rescale": a.guidance_rescale,
+                      "init_video": a.init_video, "strength": a.strength, "regen_mask": a.regen_mask, "paste_back": a.paste_back,
                       "finite": bool(torch.as_tensor(v).isfinite().all()), **extra}))
 
 
