@@ -338,6 +338,21 @@ int mmgt_accumulate_window_rows(const void* pred, float* pred_sum, float* counte
 int mmgt_accumulate_windows(const void* pred, float* pred_sum, float* counter, const int* idx, int B, int Fw, int F, int C, int Cpad,
                             int hw, int dtype, void* stream);
 
+/* Weighted window accumulation (context_fuse).  weights: fp32 [Fw] on the device, the weight of each POSITION of a window, one vector
+ * per clip.  pred_sum[row0 + r, :, idx[j]] = fmaf(weights[j], pred[r, :, j], pred_sum[...]) for r < rows, and counter[idx[j]] += weights[j] when
+ * bump_counter: the update kernels then divide the weighted sum by the sum of the weights.  pred is ((rows*Fw), hw, Cpad), rows 1 or 2 with
+ * row0 + rows <= 2 (rows = 1, row0 = 1: the conditional row of a step outside the guidance interval).  The fmaf is explicit; all weights 1 give the
+ * bits of mmgt_accumulate_window_rows.  Fw <= 256. */
+int mmgt_accumulate_window_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int Fw, int F, int C,
+                                    int Cpad, int hw, int rows, int row0, int bump_counter, int dtype, void* stream);
+
+/* The same for the B windows of a group in one launch: pred ((rows*B*Fw), hw, Cpad) in CFG row major order (rows = 1: [w0 .. w(B-1)] of CFG row
+ * row0), idx int32 [B][Fw].  A thread owns one target element and adds the windows that hold its frame in list order; counter gets each covering
+ * window's weight in list order: bitwise what B calls of mmgt_accumulate_window_weighted on the windows' own slices give, and with all weights 1
+ * the bits of mmgt_accumulate_windows.  No atomics.  B <= 256, F <= 65535. */
+int mmgt_accumulate_windows_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int B, int Fw, int F,
+                                     int C, int Cpad, int hw, int rows, int row0, int dtype, void* stream);
+
 /* ---- Stage-1 SMGA audio -> pose sampler: the element-wise glue between its Linear / attention / LayerNorm calls.
  * out = x rotated pairwise by the angle table cos_sin[(row % seq)][dim / 2][2] (cos, sin): RotaryEmbedding.rotate_queries_or_keys,
  * src/audio2pose_model/rotary_embedding_torch.py:38-61,106-113 (call sites model.py:121,267,298-299). */

@@ -403,6 +403,116 @@ extern "C" int mmgt_accumulate_windows(const void* pred, float* pred_sum, float*
   return 0;
 }
 
+namespace {
+
+// The weighted forms of accumulate_window_kernel and accumulate_windows_kernel (context_fuse): position j of a window enters the overlap average with weight w[j]
+// (fp32 [Fw], one vector per clip) and counter collects the weights, so the update kernels divide by sum w as they divide by the window count.
+// The product is an EXPLICIT fmaf in both, so that contraction cannot make the group launch differ from sequential launches; w = 1 gives the
+// bits of the unweighted kernels (fmaf(1, v, s) = s + v).  A frame index outside [0, F) is skipped.
+template <typename T>
+__global__ void accumulate_window_weighted_kernel(const T* __restrict__ pred, float* __restrict__ ps, float* __restrict__ counter,
+                                                  const int* __restrict__ idx, const float* __restrict__ w, int Fw, int F, int C, int Cpad,
+                                                  int hw, int rows, int row0, int bump) {
+  const long total = (long)rows * C * Fw * hw;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int p = i % hw;
+    long t = i / hw;
+    const int j = t % Fw;
+    t /= Fw;
+    const int c = t % C;
+    const int b = t / C;
+    const int f = idx[j];
+    if ((unsigned)f >= (unsigned)F) continue;
+    const float v = Elem<T>::ld(pred + (((long)b * Fw + j) * hw + p) * Cpad + c);
+    float* dst = ps + (((long)(row0 + b) * C + c) * F + f) * hw + p;  // window indices are distinct: no two threads share a target
+    *dst = fmaf(w[j], v, *dst);
+  }
+  if (bump && blockIdx.x == 0 && threadIdx.x < Fw) {
+    const int f = idx[threadIdx.x];
+    if ((unsigned)f < (unsigned)F) counter[f] += w[threadIdx.x];
+  }
+}
+
+// pred ((rows B Fw), hw, Cpad) in CFG row major order, written to CFG rows [row0, row0 + rows) of pred_sum: rows = 1, row0 = 1 is the
+// conditional row alone (a step outside the guidance interval).  One thread per TARGET element, the covering windows in list order.
+template <typename T>
+__global__ __launch_bounds__(256) void accumulate_windows_weighted_kernel(const T* __restrict__ pred, float* __restrict__ ps,
+                                                                          float* __restrict__ counter, const int* __restrict__ idx,
+                                                                          const float* __restrict__ w, int B, int Fw, int F, int C, int Cpad,
+                                                                          int hw, int rows, int row0) {
+  __shared__ int match[256];
+  const int f = blockIdx.y;
+  for (int k = threadIdx.x; k < B; k += blockDim.x) {
+    int j = -1;
+    for (int i = 0; i < Fw; ++i)
+      if (idx[k * Fw + i] == f) j = i;
+    match[k] = j;
+  }
+  __syncthreads();
+  const long total = (long)rows * C * hw;
+  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+  if (i < total) {
+    const int p = i % hw;
+    const long t = i / hw;
+    const int c = t % C;
+    const int r = t / C;
+    float* dst = ps + (((long)(row0 + r) * C + c) * F + f) * hw + p;
+    float acc = *dst;
+    bool any = false;
+    for (int k = 0; k < B; ++k) {
+      const int j = match[k];
+      if (j < 0) continue;
+      acc = fmaf(w[j], Elem<T>::ld(pred + ((((long)r * B + k) * Fw + j) * hw + p) * Cpad + c), acc);
+      any = true;
+    }
+    if (any) *dst = acc;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    float cnt = counter[f];
+    for (int k = 0; k < B; ++k)
+      if (match[k] >= 0) cnt += w[match[k]];
+    counter[f] = cnt;
+  }
+}
+
+}  // namespace
+
+extern "C" int mmgt_accumulate_window_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int Fw,
+                                               int F, int C, int Cpad, int hw, int rows, int row0, int bump_counter, int dtype, void* stream) {
+  MMGT_CHECK(pred && pred_sum && counter && idx && weights, "accumulate_window_weighted: null pointer");
+  MMGT_CHECK(Fw > 0 && Fw <= 256 && F >= Fw && C > 0 && Cpad >= C && hw > 0, "accumulate_window_weighted: bad sizes");
+  MMGT_CHECK(rows >= 1 && row0 >= 0 && row0 + rows <= 2, "accumulate_window_weighted: CFG rows [%d, %d) outside [0, 2)", row0, row0 + rows);
+  MMGT_CHECK(dtype == MMGT_F32 || dtype == MMGT_BF16, "accumulate_window_weighted: bad dtype");
+  const long total = (long)rows * C * Fw * hw;
+  if (dtype == MMGT_BF16)
+    hipLaunchKernelGGL(accumulate_window_weighted_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred,
+                       pred_sum, counter, idx, weights, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
+  else
+    hipLaunchKernelGGL(accumulate_window_weighted_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)pred,
+                       pred_sum, counter, idx, weights, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
+  MMGT_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int mmgt_accumulate_windows_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int B,
+                                                int Fw, int F, int C, int Cpad, int hw, int rows, int row0, int dtype, void* stream) {
+  MMGT_CHECK(pred && pred_sum && counter && idx && weights, "accumulate_windows_weighted: null pointer");
+  MMGT_CHECK(B > 0 && B <= 256, "accumulate_windows_weighted: %d windows in a group (1 .. 256)", B);
+  MMGT_CHECK(Fw > 0 && F >= Fw && F <= 65535 && C > 0 && Cpad >= C && hw > 0, "accumulate_windows_weighted: bad sizes");
+  MMGT_CHECK(rows >= 1 && row0 >= 0 && row0 + rows <= 2, "accumulate_windows_weighted: CFG rows [%d, %d) outside [0, 2)", row0, row0 + rows);
+  MMGT_CHECK(dtype == MMGT_F32 || dtype == MMGT_BF16, "accumulate_windows_weighted: bad dtype");
+  const long total = (long)rows * C * hw;
+  const dim3 grid((unsigned)((total + 255) / 256), (unsigned)F);
+  if (dtype == MMGT_BF16)
+    hipLaunchKernelGGL(accumulate_windows_weighted_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, pred_sum, counter,
+                       idx, weights, B, Fw, F, C, Cpad, hw, rows, row0);
+  else
+    hipLaunchKernelGGL(accumulate_windows_weighted_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pred, pred_sum, counter,
+                       idx, weights, B, Fw, F, C, Cpad, hw, rows, row0);
+  MMGT_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int mmgt_softmax_rows(const void* x, long ldx, void* out, long ldo, int rows, int cols, float scale, int dtype,
                                  void* stream) {
   MMGT_CHECK(x && out && rows > 0 && cols > 0, "softmax_rows: bad arguments");

@@ -170,6 +170,10 @@ _SIGS = {
     "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_accumulate_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "mmgt_accumulate_window_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                c_int, c_int, c_void_p]),
+    "mmgt_accumulate_windows_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -1093,6 +1097,63 @@ def accumulate_windows(pred, pred_sum, counter, idx, C):
     assert counter.numel() == F and counter.dtype == torch.float32 and pred_sum.dtype == torch.float32
     _check(lib().mmgt_accumulate_windows(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), B, Fw, F, C, pred.shape[3], hw,
                                          dtype_code(pred.dtype), _stream()), "mmgt_accumulate_windows")
+
+
+def _weighted_operands(what, pred, pred_sum, counter, idx, weights, C, B, Fw, rows, row0):
+    """The refusals shared by the two weighted accumulations, raised before anything is launched -> (F, hw)."""
+    _dev(pred, pred_sum, counter, idx, weights)
+    if rows not in (1, 2) or row0 not in (0, 1) or row0 + rows > 2:
+        raise RuntimeError(f"{what}: rows must be 2 (row0 = 0), or 1 with row0 in (0, 1); got rows={rows}, row0={row0}")
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"{what}: pred must be float32 or bfloat16, got {pred.dtype}")
+    if idx.dtype != torch.int32 or not idx.is_contiguous():
+        raise RuntimeError(f"{what}: idx must be contiguous int32, got {idx.dtype}")
+    if pred.dim() != 4 or not pred.is_contiguous() or pred.shape[0] != rows * B * Fw or pred.shape[3] < C:
+        raise RuntimeError(f"{what}: pred must be contiguous ({rows * B * Fw}, h, w, cpad >= {C}) for rows={rows}, {B} window(s) of {Fw} frames, "
+                           f"got {tuple(pred.shape)}")
+    if pred_sum.dtype != torch.float32 or pred_sum.dim() != 5 or not pred_sum.is_contiguous() or pred_sum.shape[0] != 2 or pred_sum.shape[1] != C:
+        raise RuntimeError(f"{what}: pred_sum must be contiguous float32 (2, {C}, F, h, w), got {pred_sum.dtype} {tuple(pred_sum.shape)}")
+    F, hw = pred_sum.shape[2], pred.shape[1] * pred.shape[2]
+    if pred_sum.shape[3] * pred_sum.shape[4] != hw:
+        raise RuntimeError(f"{what}: pred has {hw} pixels per frame, pred_sum {pred_sum.shape[3] * pred_sum.shape[4]}")
+    if counter.dtype != torch.float32 or counter.numel() != F or not counter.is_contiguous():
+        raise RuntimeError(f"{what}: counter must be contiguous float32 with {F} entries, got {counter.dtype} with {counter.numel()}")
+    if weights.dtype != torch.float32 or tuple(weights.shape) != (Fw,) or not weights.is_contiguous():
+        raise RuntimeError(f"{what}: weights must be contiguous float32 ({Fw},), one per window position, got {weights.dtype} {tuple(weights.shape)}")
+    if not 0 < Fw <= F:
+        raise RuntimeError(f"{what}: a window of {Fw} frames in a clip of {F}")
+    return F, hw
+
+
+def accumulate_window_weighted(pred, pred_sum, counter, idx, weights, C, rows=2, row0=0, bump_counter=True):
+    """`accumulate_window` with a weight per window position (include/mmgt_hip.h: mmgt_accumulate_window_weighted): pred_sum rows [row0, row0 + rows)
+    at frames idx = fmaf(weights[j], pred, pred_sum); counter[idx[j]] += weights[j] when bump_counter.  weights fp32 (Fw,) on the device."""
+    what = "accumulate_window_weighted"
+    if idx.dim() != 1:
+        raise RuntimeError(f"{what}: idx must be (Fw,), got {tuple(idx.shape)}")
+    Fw = idx.numel()
+    if Fw > 256:
+        raise RuntimeError(f"{what}: a window of {Fw} frames (1 .. 256)")
+    F, hw = _weighted_operands(what, pred, pred_sum, counter, idx, weights, C, 1, Fw, rows, row0)
+    _check(lib().mmgt_accumulate_window_weighted(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), _ptr(weights), Fw, F, C, pred.shape[3], hw,
+                                                 rows, row0, int(bool(bump_counter)), dtype_code(pred.dtype), _stream()),
+           "mmgt_accumulate_window_weighted")
+
+
+def accumulate_windows_weighted(pred, pred_sum, counter, idx, weights, C, rows=2, row0=0):
+    """`accumulate_windows` with a weight per window position and for one or both CFG rows (include/mmgt_hip.h: mmgt_accumulate_windows_weighted):
+    pred ((rows*B*Fw), h, w, cpad) in CFG row major order, idx (B, Fw) int32.  Bitwise B calls of `accumulate_window_weighted` in list order."""
+    what = "accumulate_windows_weighted"
+    if idx.dim() != 2:
+        raise RuntimeError(f"{what}: idx must be (B, Fw), got {tuple(idx.shape)}")
+    B, Fw = idx.shape
+    if not 1 <= B <= 256:
+        raise RuntimeError(f"{what}: {B} windows in a group (1 .. 256)")
+    F, hw = _weighted_operands(what, pred, pred_sum, counter, idx, weights, C, B, Fw, rows, row0)
+    if F > 65535:
+        raise RuntimeError(f"{what}: {F} frames (the launch has one grid row per frame, up to 65535)")
+    _check(lib().mmgt_accumulate_windows_weighted(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), _ptr(weights), B, Fw, F, C, pred.shape[3],
+                                                  hw, rows, row0, dtype_code(pred.dtype), _stream()), "mmgt_accumulate_windows_weighted")
 
 
 # ------------------------------------------------------------------------------------------------------------ SMGA glue

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import hip, parallel
-from .context import get_context_scheduler
+from .longclip import get_context_scheduler
 
 
 @dataclass
@@ -231,7 +231,8 @@ class Pose2VideoPipeline:
     def denoise(self, latents, timesteps, encoder_hidden_states, pose_fea, audio_tensor_pre, full_masks, face_masks,
                 lip_masks, guidance_scale, motion_scale, context_frames, context_stride, context_overlap,
                 context_schedule="uniform", num_inference_steps=None, callback=None, callback_steps=1,
-                window_group=None, cfg_split="auto", context_batch_size=1, eta=0.0, guidance_rescale=0.0, generator=None, known=None):
+                window_group=None, cfg_split="auto", context_batch_size=1, eta=0.0, guidance_rescale=0.0, generator=None, known=None,
+                context_fuse="flat", guidance_interval=None):
         """pipeline_pose2vid_long.py:494-643.  latents (1, C, L, h, w) fp32 on the GPU; returns the final latents.
 
         window_group: a torch.distributed process group (or True for the default group) turns on window-parallel sampling of
@@ -257,7 +258,26 @@ class Pose2VideoPipeline:
 
         known = (x0, z, mask) keeps a region of an existing clip: after every step's update -- whichever of the above it is -- one
         hip.known_latents launch replaces the cells where the fp32 (L, h, w) mask is 0 by sa x0 + sb z at scheduler.alpha_bar_after(t), in
-        place; the callback sees the latents after it.  Behind the last step alpha-bar is 1 and those cells are x0's bits."""
+        place; the callback sees the latents after it.  Behind the last step alpha-bar is 1 and those cells are x0's bits.
+
+        context_schedule="open", context_fuse and guidance_interval are opt-in; with none of them the loop makes the calls it always
+        made.  context_fuse = "pyramid" / "ramp" weights the positions of a window in the overlap average (longclip.fuse_weights, rounded once to
+        fp32; hip.accumulate_window_weighted / accumulate_windows_weighted add fmaf(w, pred, sum) in list order and counter collects the weights, so
+        the update kernels divide by sum w unchanged); one window is always flat.  guidance_interval = (lo, hi) guides the steps with
+        lo < (t + 1) / num_train_timesteps <= hi; on every other step ONLY the conditional row runs (cfg_row=1, with a memo of its own), its
+        prediction goes to CFG row 1 and the update runs at guidance 1 over the zero row 0 -- v is the conditional average -- without the
+        rescale's moments.  Any given guidance_interval, (0, 1) included, and any fuse but "flat" route the accumulation through the weighted
+        entries (flat: all weights 1, the same bits).  Neither is combined with window_group: raises ValueError."""
+        from .longclip import CONTEXT_FUSES, check_guidance_interval, fuse_weights, step_is_guided
+        if context_fuse not in CONTEXT_FUSES:
+            raise ValueError(f"context_fuse must be one of {', '.join(CONTEXT_FUSES)}, got context_fuse={context_fuse!r}")
+        interval = check_guidance_interval(guidance_interval)
+        if guidance_interval is not None and window_group is not None:
+            raise ValueError(f"guidance_interval={tuple(guidance_interval)} is not combined with window_group (the ranks are dealt whole CFG pairs "
+                             "or single rows of every step): use one GPU")
+        if context_fuse != "flat" and window_group is not None:
+            raise ValueError(f"context_fuse={context_fuse!r} is not combined with window_group (the weighted overlap average was never run on more "
+                             "than one rank): use context_fuse='flat' or one GPU")
         if known is not None and window_group is not None:
             raise ValueError("known= (the kept region of an init clip) is not combined with window_group: use one GPU")
         eta, guidance_rescale = float(eta), float(guidance_rescale)
@@ -280,6 +300,14 @@ class Pose2VideoPipeline:
         windows = list(sched(0, nsteps, video_length, context_frames, context_stride, context_overlap))
         win_idx = [torch.tensor(c, device=dev, dtype=torch.int32) for c in windows]
         win_long = [torch.tensor(c, device=dev, dtype=torch.long) for c in windows]
+        weighted = context_fuse != "flat" or guidance_interval is not None
+        fuse_w = None
+        if weighted:                                             # one fp32 vector per clip; a lone window is averaged with nothing: flat
+            if len({len(c) for c in windows}) != 1:
+                raise RuntimeError("context_fuse / guidance_interval: the windows of a clip must have the same length")
+            fuse_w = torch.tensor(fuse_weights(context_fuse if len(windows) > 1 else "flat", len(windows[0]), context_overlap),
+                                  dtype=torch.float64).to(torch.float32).to(dev)
+        num_train = getattr(self.scheduler, "num_train_timesteps", 1000)
         # per-window conditioning is step-invariant: gather it once -- per window (B = 1, and the units of window_group), or per group of B windows
         # in list order, cut in CFG row major order
         cond, groups = [], []
@@ -350,7 +378,30 @@ class Pose2VideoPipeline:
                 lat_g, t, encoder_hidden_states=encoder_hidden_states, audio_embedding=gd["audio"], pose_cond_fea=gd["pose"],
                 full_mask=gd["full"], face_mask=gd["face"], body_mask=gd["lips"], motion_scale=motion_scale, **kw)
 
+        def run_group_cond(gd, t):
+            """The conditional rows of a group alone (a step outside the guidance interval): (Bg, C, Fw, h, w) in with cfg_row=1, ((Bg Fw), h, w, 64)
+            out.  The conditioning is the second half of the pair's, cut once; the memo is a dict of its own (the pair's holds rows of another shape)."""
+            if "cond" not in gd:
+                n = gd["n"]
+                half = lambda t_: t_.view(2, t_.shape[0] // 2, -1)[1].contiguous()
+                pose = gd["pose"]
+                if pose is not None:
+                    pose = pose.view(2, pose.shape[0] // 2, *pose.shape[1:])[1].contiguous()
+                gd["cond"] = dict(pose=pose, audio=gd["audio"][n:].contiguous(), full=[half(m) for m in gd["full"]],
+                                  face=[half(m) for m in gd["face"]], lips=[half(m) for m in gd["lips"]])
+            cd = gd["cond"]
+            lat_g = self.scheduler.scale_model_input(latents[0][:, gd["long"]].permute(1, 0, 2, 3, 4), t).contiguous()
+            kw = dict(cfg_row=1)
+            if keep_window_state:
+                kw["window_state"] = cd.setdefault("state", {})
+            if uncond_audio_zero:
+                kw["audio_zero_rows"] = 0
+            return self.denoising_unet.denoise_window(
+                lat_g, t, encoder_hidden_states=encoder_hidden_states, audio_embedding=cd["audio"], pose_cond_fea=cd["pose"],
+                full_mask=cd["full"], face_mask=cd["face"], body_mask=cd["lips"], motion_scale=motion_scale, **kw)
+
         for i, t in enumerate(timesteps):
+            guided = step_is_guided(t, interval, num_train)
             pred_sum = torch.zeros((2,) + tuple(latents.shape[1:]), device=dev, dtype=torch.float32)
             counter = torch.zeros((video_length,), device=dev, dtype=torch.float32)
 
@@ -372,7 +423,18 @@ class Pose2VideoPipeline:
                     pose_cond_fea=cd["pose"], full_mask=cd["full"], face_mask=cd["face"], body_mask=cd["lips"],
                     motion_scale=motion_scale, **kw)
 
-            if B > 1:
+            if weighted:
+                # rows = 1, row0 = 1 on an unguided step: CFG row 0 of pred_sum keeps its zeros and counter is bumped once per window
+                rows, row0 = (2, 0) if guided else (1, 1)
+                if B > 1:
+                    for gd in groups:
+                        hip.accumulate_windows_weighted(run_group(gd, t) if guided else run_group_cond(gd, t), pred_sum, counter, gd["idx"], fuse_w, C,
+                                                        rows=rows, row0=row0)
+                else:
+                    for w in range(len(windows)):
+                        hip.accumulate_window_weighted(run_unit(w, None if guided else 1), pred_sum, counter, win_idx[w], fuse_w, C, rows=rows,
+                                                       row0=row0)
+            elif B > 1:
                 for gd in groups:
                     hip.accumulate_windows(run_group(gd, t), pred_sum, counter, gd["idx"], C)
             elif window_group is None:
@@ -396,16 +458,18 @@ class Pose2VideoPipeline:
                             w, row = units[u0 + r]
                             hip.accumulate_window(preds[r], pred_sum, counter, win_idx[w], C, rows=rows, row0=row or 0,
                                                   bump_counter=row in (None, 0))
+            # an unguided step: guidance 1 over the zero row 0 gives v = 0 + 1 (c - 0) = c, the conditional average; the rescale is the identity there
+            g_step = float(guidance_scale) if guided else 1.0
             if not general:
                 sa_t, sb_t, sa_p, sb_p = self.scheduler.step_coefficients(t)
-                latents = hip.cfg_ddim_step(pred_sum, counter, latents, float(guidance_scale), sa_t, sb_t, sa_p, sb_p)
+                latents = hip.cfg_ddim_step(pred_sum, counter, latents, g_step, sa_t, sb_t, sa_p, sb_p)
             else:
                 noise = None
                 if eta > 0.0:                                    # on the generator's device, as the initial latents (prepare_latents)
                     gdev = generator.device if isinstance(generator, torch.Generator) else dev
                     noise = torch.randn(latents.shape, generator=generator, device=gdev, dtype=torch.float32).to(dev)
-                latents = hip.sampler_step(pred_sum, counter, latents, float(guidance_scale), *self.scheduler.update_coefficients(t, eta),
-                                           rescale=guidance_rescale, noise=noise, prev_x0=x0_bufs[(i - 1) % 2] if dpm and i > 0 else None,
+                latents = hip.sampler_step(pred_sum, counter, latents, g_step, *self.scheduler.update_coefficients(t, eta),
+                                           rescale=guidance_rescale if guided else 0.0, noise=noise, prev_x0=x0_bufs[(i - 1) % 2] if dpm and i > 0 else None,
                                            x0_out=x0_bufs[i % 2] if dpm else None)
             if known is not None:
                 from .scheduler import known_scalars
@@ -422,8 +486,12 @@ class Pose2VideoPipeline:
                  generator=None, output_type: Optional[str] = "tensor", return_dict: bool = True,
                  callback: Optional[Callable] = None, callback_steps: Optional[int] = 1, context_schedule="uniform",
                  context_frames=12, context_stride=1, context_overlap=4, context_batch_size=1, interpolation_factor=1,
-                 guidance_rescale: float = 0.0, **kwargs):
+                 guidance_rescale: float = 0.0, context_fuse="flat", guidance_interval=None, **kwargs):
         self._check_update_args(float(eta), float(guidance_rescale), kwargs.get("window_group"))
+        from .longclip import CONTEXT_FUSES, check_guidance_interval
+        if context_fuse not in CONTEXT_FUSES:
+            raise ValueError(f"context_fuse must be one of {', '.join(CONTEXT_FUSES)}, got context_fuse={context_fuse!r}")
+        check_guidance_interval(guidance_interval)
         if int(context_batch_size) < 1:
             raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
         if not guidance_scale > 1.0:
@@ -507,7 +575,9 @@ class Pose2VideoPipeline:
                                context_schedule, num_inference_steps, callback, callback_steps,
                                window_group=kwargs.get("window_group"), cfg_split=kwargs.get("cfg_split", "auto"),
                                context_batch_size=context_batch_size, eta=eta, guidance_rescale=guidance_rescale,
-                               generator=generator if isinstance(generator, torch.Generator) else None, **({"known": known} if known else {}))
+                               generator=generator if isinstance(generator, torch.Generator) else None, **({"known": known} if known else {}),
+                               **({"context_fuse": context_fuse} if context_fuse != "flat" else {}),
+                               **({"guidance_interval": guidance_interval} if guidance_interval is not None else {}))
         unet.clear_banks()                                                                # :645-646
 
         if interpolation_factor > 0:

@@ -95,7 +95,9 @@ def parse_args():
     p.add_argument("--eta", type=float, default=0.0, help="DDIM's stochasticity (0 = deterministic, 1 = ancestral); not with --sampler dpmpp2m")
     p.add_argument("--guidance_rescale", type=float, default=0.0,
                    help="in [0, 1]: rescale the guided prediction to the conditional one's standard deviation (Lin et al. 2305.08891, 3.4)")
+    from mmgt_amd.longclip import add_longclip_arguments
     from mmgt_amd.inputs import add_revoice_arguments
+    add_longclip_arguments(p)
     add_revoice_arguments(p)
     return p.parse_args()
 
@@ -281,12 +283,14 @@ def main():
     elif ref_img is None:
         ref_img = Image.fromarray(((hash_uniform("a2v.ref", (a.H, a.W, 3), 0.5) + 0.5) * 255).clamp(0, 255).to(torch.uint8).numpy())
     # --init_video and its flags: the drawn 512 x 512 mask frames are the pixel masks (the pipeline resizes them to W x H)
+    from mmgt_amd.longclip import longclip_kwargs
     from mmgt_amd.inputs import revoice_kwargs
     revoice = revoice_kwargs(a, {"face": face_u8, "lips": lips_u8, "hands": _hands_u8}, a.L, dev)
     t0 = time.time()
     out = pipe(ref_img, pose, audio_tensor.float(), full, face, lips, a.W, a.H, a.L, a.steps, a.cfg,
                generator=torch.manual_seed(a.seed), motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c,
-               context_batch_size=a.context_batch_size, output_type="uint8", eta=a.eta, guidance_rescale=a.guidance_rescale, **revoice)
+               context_batch_size=a.context_batch_size, output_type="uint8", eta=a.eta, guidance_rescale=a.guidance_rescale,
+               **longclip_kwargs(a), **revoice)
     torch.cuda.synchronize()
     timing["stage2_s"] = round(time.time() - t0, 3)
     v = torch.as_tensor(out.videos)                                                                          # (1, L, H, W, 3) uint8
@@ -311,7 +315,8 @@ def main():
             extra["webp_quality"] = lossy
     print(json.dumps({"video": list(v.shape), "video_dtype": str(v.dtype), "saved": path, "slices": n_slices, "steps": a.steps,
                       "dtype": a.dtype, "context_batch_size": a.context_batch_size, "sampler": a.sampler, "eta": a.eta,
-                      "guidance_rescale": a.guidance_rescale, "init_video": a.init_video, "strength": a.strength, "regen_mask": a.regen_mask,
+                      "guidance_rescale": a.guidance_rescale, "context_schedule": a.context_schedule, "context_fuse": a.context_fuse,
+                      "guidance_interval": a.guidance_interval, "init_video": a.init_video, "strength": a.strength, "regen_mask": a.regen_mask,
                       "paste_back": a.paste_back, "keypoints_finite": bool(np.isfinite(kps).all()),
                       "mask_levels": [list(m.shape) for m in face], **timing, **extra}))
 

@@ -101,7 +101,9 @@ def parse_args():
     p.add_argument("--eta", type=float, default=0.0, help="DDIM's stochasticity (0 = deterministic, 1 = ancestral); not with --sampler dpmpp2m")
     p.add_argument("--guidance_rescale", type=float, default=0.0,
                    help="in [0, 1]: rescale the guided prediction to the conditional one's standard deviation (Lin et al. 2305.08891, 3.4)")
+    from mmgt_amd.longclip import add_longclip_arguments
     from mmgt_amd.inputs import add_revoice_arguments
+    add_longclip_arguments(p)
     add_revoice_arguments(p)
     return p.parse_args()
 
@@ -261,12 +263,14 @@ def run_files(a, dev, dtype):
     if a.decode_progressive_jpeg:
         lossy["jpeg_progressive"] = True
     revoice = revoice_kwargs(a, mask_clips(a, dev, L), L, dev, a.decoder == "device", **lossy)       # --init_video and its flags
+    from mmgt_amd.longclip import longclip_kwargs
+    longclip = longclip_kwargs(a)                              # --context_schedule, --context_fuse, --guidance_interval
     gen = torch.manual_seed(a.seed)
     torch.cuda.synchronize()
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, L, a.steps, a.cfg, generator=gen, motion_scale=[1.0, 1.0, 2.0],
                context_frames=a.num_c, context_batch_size=a.context_batch_size, output_type="jpeg" if a.format == "avi" else "uint8",
-               jpeg_quality=a.quality, eta=a.eta, guidance_rescale=a.guidance_rescale, **revoice)
+               jpeg_quality=a.quality, eta=a.eta, guidance_rescale=a.guidance_rescale, **longclip, **revoice)
     torch.cuda.synchronize()
     dt = time.time() - t0
     save_dir = os.path.join(a.out_dir, f"multi_person_{a.num_c}")
@@ -291,6 +295,7 @@ def run_files(a, dev, dtype):
     print(json.dumps({"video": shape, "saved": path, "frames": L, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
                       "steps": a.steps, "weights": "random" if a.random_weights else a.config, "dtype": a.dtype,
                       "context_batch_size": a.context_batch_size, "sampler": a.sampler, "eta": a.eta, "guidance_rescale": a.guidance_rescale,
+                      "context_schedule": a.context_schedule, "context_fuse": a.context_fuse, "guidance_interval": a.guidance_interval,
                       "init_video": a.init_video, "strength": a.strength, "regen_mask": a.regen_mask, "paste_back": a.paste_back, **extra}))
 
 
@@ -340,13 +345,15 @@ def main():
     from mmgt_amd.inputs import revoice_kwargs
     cell_px = lambda lv: (lv[0].view(a.L, lat, lat) >= 0.5).to(torch.uint8).mul(255).repeat_interleave(8, 1).repeat_interleave(8, 2)
     revoice = revoice_kwargs(a, {"face": cell_px(face), "lips": cell_px(lips), "hands": cell_px(hands) if a.hands_mask_path else None}, a.L, dev)
+    from mmgt_amd.longclip import get_context_scheduler, longclip_kwargs
+    longclip = longclip_kwargs(a)                              # --context_schedule, --context_fuse, --guidance_interval
     torch.cuda.synchronize()
     t0 = time.time()
     out = pipe(ref_img, pose, audio, full, face, lips, a.W, a.H, a.L, a.steps, a.cfg, generator=gen,
                motion_scale=[1.0, 1.0, 2.0], context_frames=a.num_c, context_batch_size=a.context_batch_size,
                output_type="uint8" if a.clip_parallel or a.paste_back else "tensor",
                decode=not a.no_decode,                         # CLIP embedding and ref_image_latents: HIP encoders, from ref_img
-               window_group=True if a.window_parallel else None, eta=a.eta, guidance_rescale=a.guidance_rescale, **revoice)
+               window_group=True if a.window_parallel else None, eta=a.eta, guidance_rescale=a.guidance_rescale, **longclip, **revoice)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if a.clip_parallel:
@@ -392,9 +399,10 @@ def main():
         frames = frames_uint8(v, 1)
         extra["png_files"] = len(write_png_sequence(extra["pngs"], encode_png_frames(frames), frames.shape[2], frames.shape[1]))
     print(json.dumps({"video": list(v.shape), "saved": path, "build_s": round(t_build, 2), "sample_s": round(dt, 3),
-                      "steps": a.steps, "windows_per_step": len(list(__import__("mmgt_amd.context", fromlist=["uniform"]).uniform(
+                      "steps": a.steps, "windows_per_step": len(list(get_context_scheduler(a.context_schedule)(
                           0, a.steps, a.L, a.num_c, 1, 4))), "context_batch_size": a.context_batch_size, "dtype": a.dtype,
                       "sampler": a.sampler, "eta": a.eta, "guidance_rescale": a.guidance_rescale,
+                      "context_schedule": a.context_schedule, "context_fuse": a.context_fuse, "guidance_interval": a.guidance_interval,
                       "init_video": a.init_video, "strength": a.strength, "regen_mask": a.regen_mask, "paste_back": a.paste_back,
                       "finite": bool(torch.as_tensor(v).isfinite().all()), **extra}))
 
