@@ -20,7 +20,7 @@ step, and the decoded frames can be composited onto the clip's own frames on the
 `output_type="jpeg"` (with `jpeg_quality=`, `jpeg_subsampling=`) returns one JPEG file (bytes) per frame, encoded on the device.
 """
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Union
 
 import numpy as np
@@ -34,6 +34,33 @@ from .longclip import get_context_scheduler
 @dataclass
 class Pose2VideoPipelineOutput:
     videos: Union[torch.Tensor, np.ndarray]
+
+
+@dataclass
+class _Unit:
+    """One forward of the sampler loop: 1 to B windows of the clip's window list, for the CFG pair (`row` None; batch rows in CFG row major order
+    [uncond w0 .. uncond w(n-1), cond w0 .. cond w(n-1)]) or for one CFG row alone (`row` 0 or 1), with its step-invariant conditioning and the memo
+    (`state`) in which the HIP operator keeps what it derives from exactly these rows."""
+    windows: List[int]                    # numbers in the window list
+    row: Optional[int]
+    long: torch.Tensor                    # (n, Fw) long: the windows' frames, for the gather from the latents
+    idx: torch.Tensor                     # the same in int32, in the shape the accumulate entry takes: (Fw,) at context_batch_size 1, else (n, Fw)
+    pose: Optional[torch.Tensor]
+    audio: torch.Tensor
+    full: List[torch.Tensor]
+    face: List[torch.Tensor]
+    lips: List[torch.Tensor]
+    state: dict = field(default_factory=dict)
+    halves: dict = field(default_factory=dict)
+
+    def half(self, row):
+        """The unit of CFG row `row` of this pair, cut on first use: every tensor of a pair is [row 0 | row 1] along its first axis.  The memo is a
+        dict of its own (the pair's holds rows of another shape)."""
+        if row not in self.halves:
+            cut = lambda t: t.view(2, t.shape[0] // 2, *t.shape[1:])[row].contiguous()
+            self.halves[row] = _Unit(self.windows, row, self.long, self.idx, None if self.pose is None else cut(self.pose), cut(self.audio),
+                                   [cut(m) for m in self.full], [cut(m) for m in self.face], [cut(m) for m in self.lips])
+        return self.halves[row]
 
 
 def _pil_to_tensor(img, width, height, normalize):
@@ -130,13 +157,9 @@ class Pose2VideoPipeline:
         from .interp import interpolate_frames
         return interpolate_frames(latents, interpolation_factor)
 
-    def _pose_window(self, pose_fea, c):
-        """Pose features of one window for both CFG rows (pipeline_pose2vid_long.py:576-580), converted ONCE to the
-        operator's channels-last layout and dtype: they are step-invariant, so the per-step forward takes them as is."""
-        return self._pose_group(pose_fea, [c])
-
     def _pose_group(self, pose_fea, cs):
-        """The same for the windows `cs` of one group, CFG row major: [w0 .. w(B-1), w0 .. w(B-1)]."""
+        """Pose features of the windows `cs` for both CFG rows (pipeline_pose2vid_long.py:576-580), CFG row major [w0 .. w(B-1), w0 .. w(B-1)],
+        converted ONCE to the operator's channels-last layout and dtype: they are step-invariant, so the per-step forward takes them as is."""
         if pose_fea is None:
             return None
         unet = self.denoising_unet
@@ -161,6 +184,45 @@ class Pose2VideoPipeline:
             raise ValueError(f"guidance_rescale must lie in [0, 1] (it blends the rescaled guidance_scale prediction with the plain one), got "
                              f"guidance_rescale={guidance_rescale}")
         return dpm
+
+    def _check_loop_args(self, eta, guidance_rescale, window_group, context_fuse, guidance_interval, context_batch_size):
+        """The refusals of the loop's options, for `__call__` (before any model is touched) and `denoise` alike
+        -> (eta, guidance_rescale, whether the scheduler is the multistep solver, the checked interval, B)."""
+        from .longclip import CONTEXT_FUSES, check_guidance_interval
+        if context_fuse not in CONTEXT_FUSES:
+            raise ValueError(f"context_fuse must be one of {', '.join(CONTEXT_FUSES)}, got context_fuse={context_fuse!r}")
+        interval = check_guidance_interval(guidance_interval)
+        if guidance_interval is not None and window_group is not None:
+            raise ValueError(f"guidance_interval={tuple(guidance_interval)} is not combined with window_group (the ranks are dealt whole CFG pairs "
+                             "or single rows of every step): use one GPU")
+        if context_fuse != "flat" and window_group is not None:
+            raise ValueError(f"context_fuse={context_fuse!r} is not combined with window_group (the weighted overlap average was never run on more "
+                             "than one rank): use context_fuse='flat' or one GPU")
+        eta, guidance_rescale = float(eta), float(guidance_rescale)
+        dpm = self._check_update_args(eta, guidance_rescale, window_group)
+        B = int(context_batch_size)
+        if B < 1:
+            raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
+        if B > 1 and window_group is not None:
+            raise ValueError("context_batch_size > 1 is not combined with window_group (window-parallel sampling deals single windows or "
+                             "single CFG rows to the ranks): use one of the two")
+        return eta, guidance_rescale, dpm, interval, B
+
+    def _cut_units(self, windows, B, video_length, pose_fea, audio, full_masks, face_masks, lip_masks, dev):
+        """The pair units of a clip: the window list in its order in groups of B (the last may be smaller), each with its conditioning gathered from
+        the full tensors in CFG row major order.  A window at B = 1 is a group of one; only its accumulate index keeps the single window's shape."""
+        units = []
+        for g0 in range(0, len(windows), B):
+            ws = list(range(g0, min(g0 + B, len(windows))))
+            if len({len(windows[w]) for w in ws}) != 1:
+                raise RuntimeError("context_batch_size > 1: the windows of a group must have the same length")
+            idx = torch.tensor([windows[w] for w in ws], device=dev, dtype=torch.int32)           # (n, Fw)
+            gl = idx.long()
+            rows = lambda t: t.view(2, video_length, -1)[:, gl].reshape(-1, t.shape[-1]).contiguous()     # (2, n, Fw, m) -> (2 n Fw, m)
+            units.append(_Unit(ws, None, gl, idx[0] if B == 1 else idx, self._pose_group(pose_fea, list(gl)),
+                               audio[:, gl].reshape(2 * len(ws), gl.shape[1], *audio.shape[2:]).contiguous(),
+                               [rows(t) for t in full_masks], [rows(t) for t in face_masks], [rows(t) for t in lip_masks]))
+        return units
 
     @staticmethod
     def _check_init_args(init_video, init_latents, strength, regen_mask, paste_back, video_length, window_group, num_images_per_prompt,
@@ -235,20 +297,25 @@ class Pose2VideoPipeline:
                 context_fuse="flat", guidance_interval=None):
         """pipeline_pose2vid_long.py:494-643.  latents (1, C, L, h, w) fp32 on the GPU; returns the final latents.
 
+        A step runs UNITS (`_Unit`): one unit is one call of the operator over 1 to B windows, for the CFG pair or for one CFG row.  The
+        scheduler's window list is taken in its order in groups of context_batch_size = B (the last group may be smaller; a window at B = 1 is a
+        group of one) and cut ONCE per call into pair units (`_cut_units`), rows in CFG row major order [uncond w0 .. uncond w(n-1), cond w0 ..
+        cond w(n-1)]; a single-row unit is a half of its pair's tensors, cut on first use.  Every unit owns its memo for the operator.  `forward`
+        is the one call of the operator, `accumulate` the one place a prediction enters pred_sum / counter, and a step is: pick its units, run
+        them in list order, update.
+
+        context_batch_size = B > 1 is the SAME sampler as B = 1 with B windows per forward: the predictions are added to pred_sum / counter
+        window by window in list order (hip.accumulate_windows), so the fp32 accumulation order of the overlap average is that of B = 1.  Only
+        the rounding inside the UNet may differ (dispatch picks tiles by the row count).  The reference's own handling of the argument is
+        inconsistent (App. C-7) and is not reproduced.  Not combined with window_group: raises ValueError.
+
         window_group: a torch.distributed process group (or True for the default group) turns on window-parallel sampling of
-        ONE long video.  The units of a DDIM step -- the windows, or with `cfg_split` the (window, CFG
-        row) pairs -- are dealt round-robin to the ranks; each round ends in ONE all-gather of the units' predictions, sliced
+        ONE long video.  The units of a DDIM step -- the windows' pairs, or with `cfg_split` both single rows of every
+        window -- are dealt round-robin to the ranks; each round ends in ONE all-gather of the units' predictions, sliced
         to the C valid channels (fp32 (rows * Fw, h, w, C): 1.57 MB per CFG row at 24 x 64 x 64 x 4), and every rank then
         accumulates ALL units in the reference's window order and applies the identical overlap-average + CFG + DDIM update --
         so the latents stay bit-identical on every rank, with no other exchange.  cfg_split: "auto" splits the CFG rows when
         that shortens the critical path (6 windows on 4 ranks: 3 rounds of half units instead of 2 rounds of whole ones).
-
-        context_batch_size = B > 1 is the SAME sampler as B = 1 with B windows per forward: the scheduler's window list is taken in its
-        order in groups of B (the last group may be smaller), one group is one call of the operator with the rows in CFG row major order
-        [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)], and the predictions are added to pred_sum / counter window by window in list
-        order (hip.accumulate_windows), so the fp32 accumulation order of the overlap average is that of B = 1.  Only the rounding inside the
-        UNet may differ (dispatch picks tiles by the row count).  The reference's own handling of the argument is inconsistent (App. C-7)
-        and is not reproduced.  Not combined with window_group: raises ValueError.
 
         The update behind the accumulation follows the scheduler's class.  A DDIMScheduler with eta = 0 and guidance_rescale = 0 is
         hip.cfg_ddim_step, as ever.  Anything else is hip.sampler_step: eta > 0 draws one fp32 noise tensor per step from `generator` (after the
@@ -268,38 +335,21 @@ class Pose2VideoPipeline:
         prediction goes to CFG row 1 and the update runs at guidance 1 over the zero row 0 -- v is the conditional average -- without the
         rescale's moments.  Any given guidance_interval, (0, 1) included, and any fuse but "flat" route the accumulation through the weighted
         entries (flat: all weights 1, the same bits).  Neither is combined with window_group: raises ValueError."""
-        from .longclip import CONTEXT_FUSES, check_guidance_interval, fuse_weights, step_is_guided
-        if context_fuse not in CONTEXT_FUSES:
-            raise ValueError(f"context_fuse must be one of {', '.join(CONTEXT_FUSES)}, got context_fuse={context_fuse!r}")
-        interval = check_guidance_interval(guidance_interval)
-        if guidance_interval is not None and window_group is not None:
-            raise ValueError(f"guidance_interval={tuple(guidance_interval)} is not combined with window_group (the ranks are dealt whole CFG pairs "
-                             "or single rows of every step): use one GPU")
-        if context_fuse != "flat" and window_group is not None:
-            raise ValueError(f"context_fuse={context_fuse!r} is not combined with window_group (the weighted overlap average was never run on more "
-                             "than one rank): use context_fuse='flat' or one GPU")
+        from .longclip import fuse_weights, step_is_guided
+        eta, guidance_rescale, dpm, interval, B = self._check_loop_args(eta, guidance_rescale, window_group, context_fuse, guidance_interval,
+                                                                        context_batch_size)
         if known is not None and window_group is not None:
             raise ValueError("known= (the kept region of an init clip) is not combined with window_group: use one GPU")
-        eta, guidance_rescale = float(eta), float(guidance_rescale)
-        dpm = self._check_update_args(eta, guidance_rescale, window_group)
-        general = dpm or eta != 0.0 or guidance_rescale != 0.0
-        x0_bufs = [torch.empty_like(latents), torch.empty_like(latents)] if dpm else None
-        B = int(context_batch_size)
-        if B < 1:
-            raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
-        if B > 1 and window_group is not None:
-            raise ValueError("context_batch_size > 1 is not combined with window_group (window-parallel sampling deals single windows or "
-                             "single CFG rows to the ranks): use one of the two")
         if B > 1 and latents.shape[0] != 1:
             raise ValueError("context_batch_size > 1 batches windows of ONE clip: latents must be (1, C, L, h, w)")
+        general = dpm or eta != 0.0 or guidance_rescale != 0.0
+        x0_bufs = [torch.empty_like(latents), torch.empty_like(latents)] if dpm else None
         video_length = latents.shape[2]
         dev = latents.device
         sched = get_context_scheduler(context_schedule)
         nsteps = num_inference_steps or len(timesteps)
         # the reference passes step = 0 at every iteration, so the windows never move (:534-543)
         windows = list(sched(0, nsteps, video_length, context_frames, context_stride, context_overlap))
-        win_idx = [torch.tensor(c, device=dev, dtype=torch.int32) for c in windows]
-        win_long = [torch.tensor(c, device=dev, dtype=torch.long) for c in windows]
         weighted = context_fuse != "flat" or guidance_interval is not None
         fuse_w = None
         if weighted:                                             # one fp32 vector per clip; a lone window is averaged with nothing: flat
@@ -308,29 +358,8 @@ class Pose2VideoPipeline:
             fuse_w = torch.tensor(fuse_weights(context_fuse if len(windows) > 1 else "flat", len(windows[0]), context_overlap),
                                   dtype=torch.float64).to(torch.float32).to(dev)
         num_train = getattr(self.scheduler, "num_train_timesteps", 1000)
-        # per-window conditioning is step-invariant: gather it once -- per window (B = 1, and the units of window_group), or per group of B windows
-        # in list order, cut in CFG row major order
-        cond, groups = [], []
-        if B == 1:
-            for c in win_long:
-                cond.append(dict(
-                    pose=self._pose_window(pose_fea, c),
-                    audio=audio_tensor_pre[:, c].contiguous(),
-                    full=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in full_masks],
-                    face=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in face_masks],
-                    lips=[t.view(2, video_length, -1)[:, c].reshape(-1, t.shape[-1]).contiguous() for t in lip_masks]))
-        else:
-            for g0 in range(0, len(windows), B):
-                ws = list(range(g0, min(g0 + B, len(windows))))
-                if len({len(windows[w]) for w in ws}) != 1:
-                    raise RuntimeError("context_batch_size > 1: the windows of a group must have the same length")
-                gl = torch.stack([win_long[w] for w in ws])                                   # (Bg, Fw)
-                rows = lambda t: t.view(2, video_length, -1)[:, gl].reshape(-1, t.shape[-1]).contiguous()     # (2, Bg, Fw, n) -> (2 Bg Fw, n)
-                groups.append(dict(
-                    n=len(ws), idx=torch.stack([win_idx[w] for w in ws]).contiguous(), long=gl,
-                    pose=self._pose_group(pose_fea, [win_long[w] for w in ws]),
-                    audio=audio_tensor_pre[:, gl].reshape(2 * len(ws), gl.shape[1], *audio_tensor_pre.shape[2:]).contiguous(),
-                    full=[rows(t) for t in full_masks], face=[rows(t) for t in face_masks], lips=[rows(t) for t in lip_masks]))
+        # per-window conditioning and the index tensors are step-invariant: cut once per call, single rows on first use
+        pairs = self._cut_units(windows, B, video_length, pose_fea, audio_tensor_pre, full_masks, face_masks, lip_masks, dev)
         # the reference's unconditional audio row is zeros_like(audio) (:484-485): checked once here (one device sync per clip), and the
         # operator then skips that row's audio cross-attention, whose result is exactly zero
         hip_op = hasattr(self.denoising_unet, "boc")                # the HIP operator (CPU doubles of the tests take no extras)
@@ -339,138 +368,87 @@ class Pose2VideoPipeline:
         keep_window_state = hip_op and bool(hip.tune_get("window_state"))
         C = latents.shape[1]
         group = world = rank = None
-        units = [(w, None) for w in range(len(windows))]
         if window_group is not None:
             group = None if window_group is True else window_group
             world, rank = parallel.dist.get_world_size(group), parallel.dist.get_rank(group)
             nw = len(windows)
             if cfg_split == "auto":
                 cfg_split = -(-2 * nw // world) < 2 * -(-nw // world)      # rounds of half units vs rounds of whole units
-            if cfg_split:
-                units = [(w, row) for w in range(nw) for row in (0, 1)]
-        half_cond = {}
+        split = window_group is not None and bool(cfg_split)
 
-        def unit_cond(w, row):
-            """Conditioning of one CFG row of window w (step-invariant, cut once)."""
-            if (w, row) not in half_cond:
-                cd, fw = cond[w], len(windows[w])
-                cut = lambda t: t.view(2, fw, -1)[row].contiguous()
-                pose = cd["pose"]
-                if pose is not None:
-                    pose = pose.view(2, fw, *pose.shape[1:])[row].contiguous() if pose.dim() == 4 else pose[row:row + 1]
-                half_cond[(w, row)] = dict(pose=pose, audio=cd["audio"][row:row + 1].contiguous(),
-                                           full=[cut(t) for t in cd["full"]], face=[cut(t) for t in cd["face"]],
-                                           lips=[cut(t) for t in cd["lips"]])
-            return half_cond[(w, row)]
-
-        def run_group(gd, t):
-            """One forward for the windows of a group: (2 Bg, C, Fw, h, w) in, ((2 Bg Fw), h, w, 64) channels-last out.  (The keyword
-            assembly repeats run_unit's on purpose: the B = 1 path stays as it was; fold the two when a default other than 1 is chosen.)"""
-            lat_g = self.scheduler.scale_model_input(latents[0][:, gd["long"]].permute(1, 0, 2, 3, 4), t).repeat(2, 1, 1, 1, 1)
+        def forward(u, t):
+            """The operator on one unit: (2 n, C, Fw, h, w) in for a pair, (n, C, Fw, h, w) with cfg_row for a single row; ((rows n Fw), h, w, 64)
+            channels-last out.  What it tells the operator is true by construction: the pair's second half is .repeat(2 ...) of the first here and
+            in _pose_group, the unconditional rows come first, and the memo is the unit's own."""
+            lat = self.scheduler.scale_model_input(latents[:, :, u.long].transpose(1, 2).flatten(0, 1), t)      # a gather: window by window
             kw = {}
-            if keep_window_state:                                # one memo per GROUP: its audio K / V and mask rows belong to these windows alone
-                kw["window_state"] = gd.setdefault("state", {})
+            if u.row is None:
+                lat = lat.repeat(2, 1, 1, 1, 1)
+            else:
+                lat = lat.contiguous()
+                kw["cfg_row"] = u.row
+            if keep_window_state:                                # the HIP operator memoises what it derives from the step-invariant inputs
+                kw["window_state"] = u.state
             if uncond_audio_zero:
-                kw["audio_zero_rows"] = gd["n"]
-            if hip_op:
-                kw["cfg_rows_share_input"] = True                # .repeat(2 ...) above and in _pose_group: the second half is a copy of the first
+                kw["audio_zero_rows"] = 0 if u.row == 1 else len(u.windows)
+            if hip_op and u.row is None:
+                kw["cfg_rows_share_input"] = True
             return self.denoising_unet.denoise_window(
-                lat_g, t, encoder_hidden_states=encoder_hidden_states, audio_embedding=gd["audio"], pose_cond_fea=gd["pose"],
-                full_mask=gd["full"], face_mask=gd["face"], body_mask=gd["lips"], motion_scale=motion_scale, **kw)
+                lat, t, encoder_hidden_states=encoder_hidden_states, audio_embedding=u.audio, pose_cond_fea=u.pose,
+                full_mask=u.full, face_mask=u.face, body_mask=u.lips, motion_scale=motion_scale, **kw)
 
-        def run_group_cond(gd, t):
-            """The conditional rows of a group alone (a step outside the guidance interval): (Bg, C, Fw, h, w) in with cfg_row=1, ((Bg Fw), h, w, 64)
-            out.  The conditioning is the second half of the pair's, cut once; the memo is a dict of its own (the pair's holds rows of another shape)."""
-            if "cond" not in gd:
-                n = gd["n"]
-                half = lambda t_: t_.view(2, t_.shape[0] // 2, -1)[1].contiguous()
-                pose = gd["pose"]
-                if pose is not None:
-                    pose = pose.view(2, pose.shape[0] // 2, *pose.shape[1:])[1].contiguous()
-                gd["cond"] = dict(pose=pose, audio=gd["audio"][n:].contiguous(), full=[half(m) for m in gd["full"]],
-                                  face=[half(m) for m in gd["face"]], lips=[half(m) for m in gd["lips"]])
-            cd = gd["cond"]
-            lat_g = self.scheduler.scale_model_input(latents[0][:, gd["long"]].permute(1, 0, 2, 3, 4), t).contiguous()
-            kw = dict(cfg_row=1)
-            if keep_window_state:
-                kw["window_state"] = cd.setdefault("state", {})
-            if uncond_audio_zero:
-                kw["audio_zero_rows"] = 0
-            return self.denoising_unet.denoise_window(
-                lat_g, t, encoder_hidden_states=encoder_hidden_states, audio_embedding=cd["audio"], pose_cond_fea=cd["pose"],
-                full_mask=cd["full"], face_mask=cd["face"], body_mask=cd["lips"], motion_scale=motion_scale, **kw)
+        def accumulate(u, pred, pred_sum, counter):
+            """One unit's prediction into pred_sum / counter.  The entry follows the call's options, not the unit's size (a lone last group is a group
+            of one).  A single row goes to its own CFG row; of a cfg_split pair only row 0 bumps the counter, an unguided step's row 1 bumps it itself."""
+            rows, row0 = (2, 0) if u.row is None else (1, u.row)
+            if weighted and B > 1:
+                hip.accumulate_windows_weighted(pred, pred_sum, counter, u.idx, fuse_w, C, rows=rows, row0=row0)
+            elif weighted:
+                hip.accumulate_window_weighted(pred, pred_sum, counter, u.idx, fuse_w, C, rows=rows, row0=row0)
+            elif B > 1:
+                hip.accumulate_windows(pred, pred_sum, counter, u.idx, C)
+            else:
+                hip.accumulate_window(pred, pred_sum, counter, u.idx, C, rows=rows, row0=row0, bump_counter=u.row in (None, 0))
+
+        def update(i, t, guided, pred_sum, counter):
+            """Overlap average + CFG + the scheduler's update -> the next latents.  An unguided step: guidance 1 over the zero row 0 gives
+            v = 0 + 1 (c - 0) = c, the conditional average; the rescale is the identity there."""
+            g_step = float(guidance_scale) if guided else 1.0
+            if not general:
+                return hip.cfg_ddim_step(pred_sum, counter, latents, g_step, *self.scheduler.step_coefficients(t))
+            noise = None
+            if eta > 0.0:                                        # on the generator's device, as the initial latents (prepare_latents)
+                gdev = generator.device if isinstance(generator, torch.Generator) else dev
+                noise = torch.randn(latents.shape, generator=generator, device=gdev, dtype=torch.float32).to(dev)
+            return hip.sampler_step(pred_sum, counter, latents, g_step, *self.scheduler.update_coefficients(t, eta),
+                                    rescale=guidance_rescale if guided else 0.0, noise=noise, prev_x0=x0_bufs[(i - 1) % 2] if dpm and i > 0 else None,
+                                    x0_out=x0_bufs[i % 2] if dpm else None)
 
         for i, t in enumerate(timesteps):
             guided = step_is_guided(t, interval, num_train)
             pred_sum = torch.zeros((2,) + tuple(latents.shape[1:]), device=dev, dtype=torch.float32)
             counter = torch.zeros((video_length,), device=dev, dtype=torch.float32)
-
-            def run_unit(w, row):
-                lat_w = self.scheduler.scale_model_input(latents[:, :, win_long[w]], t)
-                if row is None:
-                    cd, kw = cond[w], {}
-                    lat_w = lat_w.repeat(2, 1, 1, 1, 1)
-                else:
-                    cd, kw = unit_cond(w, row), dict(cfg_row=row)
-                if keep_window_state:                            # the HIP operator memoises what it derives from the step-invariant inputs
-                    kw["window_state"] = cd.setdefault("state", {})
-                if uncond_audio_zero:
-                    kw["audio_zero_rows"] = 1 if row in (None, 0) else 0
-                if hip_op and row is None:
-                    kw["cfg_rows_share_input"] = True            # lat_w.repeat(2 ...) above, pose.repeat(2 ...) in _pose_window
-                return self.denoising_unet.denoise_window(
-                    lat_w, t, encoder_hidden_states=encoder_hidden_states, audio_embedding=cd["audio"],
-                    pose_cond_fea=cd["pose"], full_mask=cd["full"], face_mask=cd["face"], body_mask=cd["lips"],
-                    motion_scale=motion_scale, **kw)
-
-            if weighted:
-                # rows = 1, row0 = 1 on an unguided step: CFG row 0 of pred_sum keeps its zeros and counter is bumped once per window
-                rows, row0 = (2, 0) if guided else (1, 1)
-                if B > 1:
-                    for gd in groups:
-                        hip.accumulate_windows_weighted(run_group(gd, t) if guided else run_group_cond(gd, t), pred_sum, counter, gd["idx"], fuse_w, C,
-                                                        rows=rows, row0=row0)
-                else:
-                    for w in range(len(windows)):
-                        hip.accumulate_window_weighted(run_unit(w, None if guided else 1), pred_sum, counter, win_idx[w], fuse_w, C, rows=rows,
-                                                       row0=row0)
-            elif B > 1:
-                for gd in groups:
-                    hip.accumulate_windows(run_group(gd, t), pred_sum, counter, gd["idx"], C)
-            elif window_group is None:
-                for w in range(len(windows)):
-                    hip.accumulate_window(run_unit(w, None), pred_sum, counter, win_idx[w], C)
+            # the step's units, in window list order: the pairs; their conditional rows alone on an unguided step; both rows of every pair for cfg_split
+            if split:
+                units = [p.half(row) for p in pairs for row in (0, 1)]
             else:
-                rows = 1 if units[0][1] is not None else 2
-                fw = len(windows[0])
-                wire_shape = (rows * fw,) + tuple(latents.shape[3:]) + (C,)
+                units = pairs if guided else [p.half(1) for p in pairs]
+            if window_group is None:
+                for u in units:
+                    accumulate(u, forward(u, t), pred_sum, counter)
+            else:                                                # dealt round-robin to the ranks; every rank accumulates ALL units of a round
+                wire_shape = ((1 if split else 2) * len(windows[0]),) + tuple(latents.shape[3:]) + (C,)
                 for u0 in range(0, len(units), world):
-                    mine = u0 + rank
-                    if mine < len(units):
+                    if u0 + rank < len(units):
                         # the operator returns ((rows * Fw), h, w, 64) channels-last with C valid channels: only those travel
-                        pred = run_unit(*units[mine])[..., :C].float().contiguous()
+                        pred = forward(units[u0 + rank], t)[..., :C].float().contiguous()
                         assert pred.shape == wire_shape, (pred.shape, wire_shape)
                     else:                                   # idle rank in the last round: same shape and dtype on the wire
                         pred = torch.zeros(wire_shape, device=dev, dtype=torch.float32)
                     preds = parallel.allgather_window_predictions(pred, group)
-                    for r in range(world):
-                        if u0 + r < len(units):
-                            w, row = units[u0 + r]
-                            hip.accumulate_window(preds[r], pred_sum, counter, win_idx[w], C, rows=rows, row0=row or 0,
-                                                  bump_counter=row in (None, 0))
-            # an unguided step: guidance 1 over the zero row 0 gives v = 0 + 1 (c - 0) = c, the conditional average; the rescale is the identity there
-            g_step = float(guidance_scale) if guided else 1.0
-            if not general:
-                sa_t, sb_t, sa_p, sb_p = self.scheduler.step_coefficients(t)
-                latents = hip.cfg_ddim_step(pred_sum, counter, latents, g_step, sa_t, sb_t, sa_p, sb_p)
-            else:
-                noise = None
-                if eta > 0.0:                                    # on the generator's device, as the initial latents (prepare_latents)
-                    gdev = generator.device if isinstance(generator, torch.Generator) else dev
-                    noise = torch.randn(latents.shape, generator=generator, device=gdev, dtype=torch.float32).to(dev)
-                latents = hip.sampler_step(pred_sum, counter, latents, g_step, *self.scheduler.update_coefficients(t, eta),
-                                           rescale=guidance_rescale if guided else 0.0, noise=noise, prev_x0=x0_bufs[(i - 1) % 2] if dpm and i > 0 else None,
-                                           x0_out=x0_bufs[i % 2] if dpm else None)
+                    for u, p in zip(units[u0:u0 + world], preds):
+                        accumulate(u, p, pred_sum, counter)
+            latents = update(i, t, guided, pred_sum, counter)
             if known is not None:
                 from .scheduler import known_scalars
                 hip.known_latents(known[0], known[1], *known_scalars(self.scheduler.alpha_bar_after(t)), x=latents, mask=known[2], out=latents)
@@ -487,13 +465,7 @@ class Pose2VideoPipeline:
                  callback: Optional[Callable] = None, callback_steps: Optional[int] = 1, context_schedule="uniform",
                  context_frames=12, context_stride=1, context_overlap=4, context_batch_size=1, interpolation_factor=1,
                  guidance_rescale: float = 0.0, context_fuse="flat", guidance_interval=None, **kwargs):
-        self._check_update_args(float(eta), float(guidance_rescale), kwargs.get("window_group"))
-        from .longclip import CONTEXT_FUSES, check_guidance_interval
-        if context_fuse not in CONTEXT_FUSES:
-            raise ValueError(f"context_fuse must be one of {', '.join(CONTEXT_FUSES)}, got context_fuse={context_fuse!r}")
-        check_guidance_interval(guidance_interval)
-        if int(context_batch_size) < 1:
-            raise ValueError(f"context_batch_size must be at least 1, got {context_batch_size}")
+        self._check_loop_args(eta, guidance_rescale, kwargs.get("window_group"), context_fuse, guidance_interval, context_batch_size)
         if not guidance_scale > 1.0:
             raise NotImplementedError("classifier-free guidance is mandatory in the reference loop (App. C-7)")
         init_video, init_latents, regen_mask = kwargs.get("init_video"), kwargs.get("init_latents"), kwargs.get("regen_mask")
@@ -575,9 +547,8 @@ class Pose2VideoPipeline:
                                context_schedule, num_inference_steps, callback, callback_steps,
                                window_group=kwargs.get("window_group"), cfg_split=kwargs.get("cfg_split", "auto"),
                                context_batch_size=context_batch_size, eta=eta, guidance_rescale=guidance_rescale,
-                               generator=generator if isinstance(generator, torch.Generator) else None, **({"known": known} if known else {}),
-                               **({"context_fuse": context_fuse} if context_fuse != "flat" else {}),
-                               **({"guidance_interval": guidance_interval} if guidance_interval is not None else {}))
+                               generator=generator if isinstance(generator, torch.Generator) else None, known=known,
+                               context_fuse=context_fuse, guidance_interval=guidance_interval)
         unet.clear_banks()                                                                # :645-646
 
         if interpolation_factor > 0:
