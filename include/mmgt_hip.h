@@ -320,38 +320,24 @@ int mmgt_feather_alpha(const float* cells, unsigned char* alpha, int L, int h, i
  * orig's bytes, a = 255 gen's. */
 int mmgt_composite_u8(const unsigned char* gen, const unsigned char* orig, const unsigned char* alpha, unsigned char* out, long npix, void* stream);
 
-/* pred_sum[:, :, idx[j]] += pred[:, :, j]; counter[idx[j]] += 1 for a window of Fw frames (closed-loop indices).
- * pred is channels-last T ((2*Fw), hw, Cpad) as produced by the UNet; pred_sum fp32 (2, C, F, hw).
+/* One window of Fw frames into the overlap average: pred_sum[row0 + r, :, idx[j]] = fmaf(weights[j], pred[r, :, j], pred_sum[...]) for r < rows,
+ * and counter[idx[j]] += weights[j] when bump_counter; the update kernels divide the sum by counter.  pred is channels-last T ((rows*Fw), hw, Cpad)
+ * as produced by the UNet, pred_sum fp32 (2, C, F, hw), idx int32 [Fw] of distinct frames (one outside [0, F) is skipped).  rows is 1 or 2 with
+ * row0 + rows <= 2: the CFG pair, or one CFG row (the window-parallel sampler exchanges single rows sliced to Cpad == C and passes
+ * bump_counter = 0 for a window's second row, so that counter counts windows as :624 does; rows = 1, row0 = 1 is also the conditional row of a step
+ * outside the guidance interval).  weights: fp32 [Fw] on the device, the weight of each POSITION of a window (context_fuse), or NULL
+ * for 1 everywhere: the plain add.  The fmaf is explicit, so all weights 1 give the bits of NULL.  Fw <= 256.
  * Replaces: src/pipelines/pipeline_pose2vid_long.py:622-624. */
-int mmgt_accumulate_window(const void* pred, float* pred_sum, float* counter, const int* idx, int Fw, int F, int C,
-                           int Cpad, int hw, int dtype, void* stream);
+int mmgt_accumulate_window(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int Fw, int F, int C, int Cpad,
+                           int hw, int rows, int row0, int bump_counter, int dtype, void* stream);
 
-/* The same for `rows` (1 or 2) CFG rows of pred_sum starting at row0: pred is ((rows*Fw), hw, Cpad).  The window-parallel
- * sampler (one long video over several GPUs) exchanges single CFG rows sliced to Cpad == C and accumulates them one by
- * one; bump_counter = 0 for the second row of a window so that counter counts windows, as :624 does. */
-int mmgt_accumulate_window_rows(const void* pred, float* pred_sum, float* counter, const int* idx, int Fw, int F, int C,
-                                int Cpad, int hw, int rows, int row0, int bump_counter, int dtype, void* stream);
-
-/* The B windows of one sampler group (context_batch_size = B) in one launch: pred is ((2*B*Fw), hw, Cpad) in CFG row major order
- * [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)], idx int32 [B][Fw].  The windows are added in list order (they may share frames) and
- * counter is bumped once per window: bitwise what B calls of mmgt_accumulate_window on the windows' own slices give.  No atomics. */
-int mmgt_accumulate_windows(const void* pred, float* pred_sum, float* counter, const int* idx, int B, int Fw, int F, int C, int Cpad,
-                            int hw, int dtype, void* stream);
-
-/* Weighted window accumulation (context_fuse).  weights: fp32 [Fw] on the device, the weight of each POSITION of a window, one vector
- * per clip.  pred_sum[row0 + r, :, idx[j]] = fmaf(weights[j], pred[r, :, j], pred_sum[...]) for r < rows, and counter[idx[j]] += weights[j] when
- * bump_counter: the update kernels then divide the weighted sum by the sum of the weights.  pred is ((rows*Fw), hw, Cpad), rows 1 or 2 with
- * row0 + rows <= 2 (rows = 1, row0 = 1: the conditional row of a step outside the guidance interval).  The fmaf is explicit; all weights 1 give the
- * bits of mmgt_accumulate_window_rows.  Fw <= 256. */
-int mmgt_accumulate_window_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int Fw, int F, int C,
-                                    int Cpad, int hw, int rows, int row0, int bump_counter, int dtype, void* stream);
-
-/* The same for the B windows of a group in one launch: pred ((rows*B*Fw), hw, Cpad) in CFG row major order (rows = 1: [w0 .. w(B-1)] of CFG row
- * row0), idx int32 [B][Fw].  A thread owns one target element and adds the windows that hold its frame in list order; counter gets each covering
- * window's weight in list order: bitwise what B calls of mmgt_accumulate_window_weighted on the windows' own slices give, and with all weights 1
- * the bits of mmgt_accumulate_windows.  No atomics.  B <= 256, F <= 65535. */
-int mmgt_accumulate_windows_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int B, int Fw, int F,
-                                     int C, int Cpad, int hw, int rows, int row0, int dtype, void* stream);
+/* The same for the B windows of one sampler group (context_batch_size = B) in one launch: pred ((rows*B*Fw), hw, Cpad) in CFG row major order
+ * (rows = 2: [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)]; rows = 1: [w0 .. w(B-1)] of CFG row row0), idx int32 [B][Fw].  The windows may
+ * share frames: a thread owns one target element and adds the windows that hold its frame in list order, and counter gets each covering window's
+ * weight in that order (always; there is no bump_counter).  Bitwise what B calls of mmgt_accumulate_window on the windows' own slices give; weights
+ * as there, NULL included.  A frame that no window covers keeps its bits.  No atomics.  B <= 256, F <= 65535. */
+int mmgt_accumulate_windows(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int B, int Fw, int F, int C,
+                            int Cpad, int hw, int rows, int row0, int dtype, void* stream);
 
 /* ---- Stage-1 SMGA audio -> pose sampler: the element-wise glue between its Linear / attention / LayerNorm calls.
  * out = x rotated pairwise by the angle table cos_sin[(row % seq)][dim / 2][2] (cos, sin): RotaryEmbedding.rotate_queries_or_keys,

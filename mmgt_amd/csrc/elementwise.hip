@@ -104,10 +104,17 @@ __global__ void cfg_ddim_kernel(const float* __restrict__ ps, const float* __res
   }
 }
 
+// Window accumulation (include/mmgt_hip.h: mmgt_accumulate_window, mmgt_accumulate_windows; context_fuse: DESIGN 4q).  Position j of a window
+// enters the overlap average with weight w[j] (fp32 [Fw], one vector per clip) and counter collects the weights, so the update kernels divide by
+// sum w as they divide by the window count.  w == nullptr is weight 1 at every position and loads nothing in its place.  The product is an EXPLICIT
+// fmaf in both kernels, so that contraction cannot make the group launch differ from sequential launches; fmaf(1, v, s) = s + v, so a vector of
+// ones gives the bits of nullptr.  A frame index outside [0, F) is skipped.
+//
+// The scatter kernel: ONE window, pred ((rows Fw), hw, Cpad) into CFG rows [row0, row0 + rows) of ps, grid-stride over the window's elements.
 template <typename T>
 __global__ void accumulate_window_kernel(const T* __restrict__ pred, float* __restrict__ ps, float* __restrict__ counter,
-                                         const int* __restrict__ idx, int Fw, int F, int C, int Cpad, int hw, int rows,
-                                         int row0, int bump) {
+                                         const int* __restrict__ idx, const float* __restrict__ w, int Fw, int F, int C, int Cpad, int hw,
+                                         int rows, int row0, int bump) {
   const long total = (long)rows * C * Fw * hw;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int p = i % hw;
@@ -116,43 +123,53 @@ __global__ void accumulate_window_kernel(const T* __restrict__ pred, float* __re
     t /= Fw;
     const int c = t % C;
     const int b = t / C;
+    const int f = idx[j];
+    if ((unsigned)f >= (unsigned)F) continue;
     const float v = Elem<T>::ld(pred + (((long)b * Fw + j) * hw + p) * Cpad + c);
-    ps[(((long)(row0 + b) * C + c) * F + idx[j]) * hw + p] += v;  // window indices are distinct: no two threads share a target
+    float* dst = ps + (((long)(row0 + b) * C + c) * F + f) * hw + p;  // window indices are distinct: no two threads share a target
+    *dst = fmaf(w ? w[j] : 1.f, v, *dst);
   }
-  if (bump && blockIdx.x == 0 && threadIdx.x < Fw) counter[idx[threadIdx.x]] += 1.f;
+  if (bump && blockIdx.x == 0 && threadIdx.x < Fw) {
+    const int f = idx[threadIdx.x];
+    if ((unsigned)f < (unsigned)F) counter[f] += w ? w[threadIdx.x] : 1.f;
+  }
 }
 
-// The B windows of one sampler group in ONE launch (context_batch_size = B): pred ((2 B Fw), hw, Cpad) in CFG row major order [uncond w0 ..
-// uncond w(B-1), cond w0 .. cond w(B-1)], idx [B][Fw].  Windows of a group may share frames, and the order of the fp32 adds is part of the
-// sampler's definition, so a thread owns one TARGET element (row, c, frame, pixel) and adds the windows that hold its frame in list order:
-// no atomics, bitwise what B launches of accumulate_window_kernel give.  blockIdx.y = target frame; match[k] = position of that frame in
-// window k (indices are distinct inside a window) or -1.
+// The gather kernel: the B windows of one sampler group in ONE launch (context_batch_size = B).  pred ((rows B Fw), hw, Cpad) in CFG row major
+// order (rows = 2: [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)]; rows = 1, row0 = 1: the conditional row alone, a step outside the
+// guidance interval), idx [B][Fw].  Windows of a group may share frames, and the order of the fp32 adds is part of the sampler's definition, so a
+// thread owns one TARGET element (row, c, frame, pixel) and adds the windows that hold its frame in list order: no atomics, bitwise what B launches
+// of accumulate_window_kernel give.  blockIdx.y = target frame; match[k] = position of that frame in window k (indices are distinct inside a
+// window) or -1, wk[k] = its weight there.  A target that no window covers is not stored.
 template <typename T>
 __global__ __launch_bounds__(256) void accumulate_windows_kernel(const T* __restrict__ pred, float* __restrict__ ps, float* __restrict__ counter,
-                                                                 const int* __restrict__ idx, int B, int Fw, int F, int C, int Cpad, int hw) {
+                                                                 const int* __restrict__ idx, const float* __restrict__ w, int B, int Fw, int F,
+                                                                 int C, int Cpad, int hw, int rows, int row0) {
   __shared__ int match[256];
+  __shared__ float wk[256];      // the weight of this frame in window k: read once per block, so the element loop below never looks at w
   const int f = blockIdx.y;
   for (int k = threadIdx.x; k < B; k += blockDim.x) {
     int j = -1;
     for (int i = 0; i < Fw; ++i)
       if (idx[k * Fw + i] == f) j = i;
     match[k] = j;
+    wk[k] = w && j >= 0 ? w[j] : 1.f;
   }
   __syncthreads();
-  const long total = 2L * C * hw;
+  const long total = (long)rows * C * hw;
   const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
   if (i < total) {
     const int p = i % hw;
     const long t = i / hw;
     const int c = t % C;
     const int r = t / C;
-    float* dst = ps + (((long)r * C + c) * F + f) * hw + p;
+    float* dst = ps + (((long)(row0 + r) * C + c) * F + f) * hw + p;
     float acc = *dst;
     bool any = false;
     for (int k = 0; k < B; ++k) {
       const int j = match[k];
       if (j < 0) continue;
-      acc += Elem<T>::ld(pred + ((((long)r * B + k) * Fw + j) * hw + p) * Cpad + c);
+      acc = fmaf(wk[k], Elem<T>::ld(pred + ((((long)r * B + k) * Fw + j) * hw + p) * Cpad + c), acc);
       any = true;
     }
     if (any) *dst = acc;
@@ -160,7 +177,7 @@ __global__ __launch_bounds__(256) void accumulate_windows_kernel(const T* __rest
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     float cnt = counter[f];
     for (int k = 0; k < B; ++k)
-      if (match[k] >= 0) cnt += 1.f;
+      if (match[k] >= 0) cnt += wk[k];
     counter[f] = cnt;
   }
 }
@@ -362,153 +379,38 @@ extern "C" int mmgt_cfg_ddim_step(const float* pred_sum, const float* counter, c
   return 0;
 }
 
-extern "C" int mmgt_accumulate_window_rows(const void* pred, float* pred_sum, float* counter, const int* idx, int Fw, int F,
-                                           int C, int Cpad, int hw, int rows, int row0, int bump_counter, int dtype,
-                                           void* stream) {
+extern "C" int mmgt_accumulate_window(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int Fw, int F, int C,
+                                      int Cpad, int hw, int rows, int row0, int bump_counter, int dtype, void* stream) {
   MMGT_CHECK(pred && pred_sum && counter && idx, "accumulate_window: null pointer");
   MMGT_CHECK(Fw > 0 && Fw <= 256 && F >= Fw && C > 0 && Cpad >= C && hw > 0, "accumulate_window: bad sizes");
   MMGT_CHECK(rows >= 1 && row0 >= 0 && row0 + rows <= 2, "accumulate_window: CFG rows [%d, %d) outside [0, 2)", row0, row0 + rows);
   MMGT_CHECK(dtype == MMGT_F32 || dtype == MMGT_BF16, "accumulate_window: bad dtype");
   const long total = (long)rows * C * Fw * hw;
   if (dtype == MMGT_BF16)
-    hipLaunchKernelGGL(accumulate_window_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)pred, pred_sum, counter, idx, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
+    hipLaunchKernelGGL(accumulate_window_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, pred_sum,
+                       counter, idx, weights, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
   else
-    hipLaunchKernelGGL(accumulate_window_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)pred, pred_sum, counter, idx, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
+    hipLaunchKernelGGL(accumulate_window_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)pred, pred_sum,
+                       counter, idx, weights, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
   MMGT_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int mmgt_accumulate_window(const void* pred, float* pred_sum, float* counter, const int* idx, int Fw, int F,
-                                      int C, int Cpad, int hw, int dtype, void* stream) {
-  return mmgt_accumulate_window_rows(pred, pred_sum, counter, idx, Fw, F, C, Cpad, hw, 2, 0, 1, dtype, stream);
-}
-
-extern "C" int mmgt_accumulate_windows(const void* pred, float* pred_sum, float* counter, const int* idx, int B, int Fw, int F, int C,
-                                       int Cpad, int hw, int dtype, void* stream) {
+extern "C" int mmgt_accumulate_windows(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int B, int Fw, int F,
+                                       int C, int Cpad, int hw, int rows, int row0, int dtype, void* stream) {
   MMGT_CHECK(pred && pred_sum && counter && idx, "accumulate_windows: null pointer");
   MMGT_CHECK(B > 0 && B <= 256, "accumulate_windows: %d windows in a group (1 .. 256)", B);
   MMGT_CHECK(Fw > 0 && F >= Fw && F <= 65535 && C > 0 && Cpad >= C && hw > 0, "accumulate_windows: bad sizes");
+  MMGT_CHECK(rows >= 1 && row0 >= 0 && row0 + rows <= 2, "accumulate_windows: CFG rows [%d, %d) outside [0, 2)", row0, row0 + rows);
   MMGT_CHECK(dtype == MMGT_F32 || dtype == MMGT_BF16, "accumulate_windows: bad dtype");
-  const long total = 2L * C * hw;
+  const long total = (long)rows * C * hw;
   const dim3 grid((unsigned)((total + 255) / 256), (unsigned)F);
   if (dtype == MMGT_BF16)
     hipLaunchKernelGGL(accumulate_windows_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, pred_sum, counter, idx,
-                       B, Fw, F, C, Cpad, hw);
+                       weights, B, Fw, F, C, Cpad, hw, rows, row0);
   else
     hipLaunchKernelGGL(accumulate_windows_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pred, pred_sum, counter, idx,
-                       B, Fw, F, C, Cpad, hw);
-  MMGT_LAUNCH_CHECK();
-  return 0;
-}
-
-namespace {
-
-// The weighted forms of accumulate_window_kernel and accumulate_windows_kernel (context_fuse): position j of a window enters the overlap average with weight w[j]
-// (fp32 [Fw], one vector per clip) and counter collects the weights, so the update kernels divide by sum w as they divide by the window count.
-// The product is an EXPLICIT fmaf in both, so that contraction cannot make the group launch differ from sequential launches; w = 1 gives the
-// bits of the unweighted kernels (fmaf(1, v, s) = s + v).  A frame index outside [0, F) is skipped.
-template <typename T>
-__global__ void accumulate_window_weighted_kernel(const T* __restrict__ pred, float* __restrict__ ps, float* __restrict__ counter,
-                                                  const int* __restrict__ idx, const float* __restrict__ w, int Fw, int F, int C, int Cpad,
-                                                  int hw, int rows, int row0, int bump) {
-  const long total = (long)rows * C * Fw * hw;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int p = i % hw;
-    long t = i / hw;
-    const int j = t % Fw;
-    t /= Fw;
-    const int c = t % C;
-    const int b = t / C;
-    const int f = idx[j];
-    if ((unsigned)f >= (unsigned)F) continue;
-    const float v = Elem<T>::ld(pred + (((long)b * Fw + j) * hw + p) * Cpad + c);
-    float* dst = ps + (((long)(row0 + b) * C + c) * F + f) * hw + p;  // window indices are distinct: no two threads share a target
-    *dst = fmaf(w[j], v, *dst);
-  }
-  if (bump && blockIdx.x == 0 && threadIdx.x < Fw) {
-    const int f = idx[threadIdx.x];
-    if ((unsigned)f < (unsigned)F) counter[f] += w[threadIdx.x];
-  }
-}
-
-// pred ((rows B Fw), hw, Cpad) in CFG row major order, written to CFG rows [row0, row0 + rows) of pred_sum: rows = 1, row0 = 1 is the
-// conditional row alone (a step outside the guidance interval).  One thread per TARGET element, the covering windows in list order.
-template <typename T>
-__global__ __launch_bounds__(256) void accumulate_windows_weighted_kernel(const T* __restrict__ pred, float* __restrict__ ps,
-                                                                          float* __restrict__ counter, const int* __restrict__ idx,
-                                                                          const float* __restrict__ w, int B, int Fw, int F, int C, int Cpad,
-                                                                          int hw, int rows, int row0) {
-  __shared__ int match[256];
-  const int f = blockIdx.y;
-  for (int k = threadIdx.x; k < B; k += blockDim.x) {
-    int j = -1;
-    for (int i = 0; i < Fw; ++i)
-      if (idx[k * Fw + i] == f) j = i;
-    match[k] = j;
-  }
-  __syncthreads();
-  const long total = (long)rows * C * hw;
-  const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i < total) {
-    const int p = i % hw;
-    const long t = i / hw;
-    const int c = t % C;
-    const int r = t / C;
-    float* dst = ps + (((long)(row0 + r) * C + c) * F + f) * hw + p;
-    float acc = *dst;
-    bool any = false;
-    for (int k = 0; k < B; ++k) {
-      const int j = match[k];
-      if (j < 0) continue;
-      acc = fmaf(w[j], Elem<T>::ld(pred + ((((long)r * B + k) * Fw + j) * hw + p) * Cpad + c), acc);
-      any = true;
-    }
-    if (any) *dst = acc;
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    float cnt = counter[f];
-    for (int k = 0; k < B; ++k)
-      if (match[k] >= 0) cnt += w[match[k]];
-    counter[f] = cnt;
-  }
-}
-
-}  // namespace
-
-extern "C" int mmgt_accumulate_window_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int Fw,
-                                               int F, int C, int Cpad, int hw, int rows, int row0, int bump_counter, int dtype, void* stream) {
-  MMGT_CHECK(pred && pred_sum && counter && idx && weights, "accumulate_window_weighted: null pointer");
-  MMGT_CHECK(Fw > 0 && Fw <= 256 && F >= Fw && C > 0 && Cpad >= C && hw > 0, "accumulate_window_weighted: bad sizes");
-  MMGT_CHECK(rows >= 1 && row0 >= 0 && row0 + rows <= 2, "accumulate_window_weighted: CFG rows [%d, %d) outside [0, 2)", row0, row0 + rows);
-  MMGT_CHECK(dtype == MMGT_F32 || dtype == MMGT_BF16, "accumulate_window_weighted: bad dtype");
-  const long total = (long)rows * C * Fw * hw;
-  if (dtype == MMGT_BF16)
-    hipLaunchKernelGGL(accumulate_window_weighted_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred,
-                       pred_sum, counter, idx, weights, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
-  else
-    hipLaunchKernelGGL(accumulate_window_weighted_kernel<float>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, (const float*)pred,
-                       pred_sum, counter, idx, weights, Fw, F, C, Cpad, hw, rows, row0, bump_counter);
-  MMGT_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int mmgt_accumulate_windows_weighted(const void* pred, float* pred_sum, float* counter, const int* idx, const float* weights, int B,
-                                                int Fw, int F, int C, int Cpad, int hw, int rows, int row0, int dtype, void* stream) {
-  MMGT_CHECK(pred && pred_sum && counter && idx && weights, "accumulate_windows_weighted: null pointer");
-  MMGT_CHECK(B > 0 && B <= 256, "accumulate_windows_weighted: %d windows in a group (1 .. 256)", B);
-  MMGT_CHECK(Fw > 0 && F >= Fw && F <= 65535 && C > 0 && Cpad >= C && hw > 0, "accumulate_windows_weighted: bad sizes");
-  MMGT_CHECK(rows >= 1 && row0 >= 0 && row0 + rows <= 2, "accumulate_windows_weighted: CFG rows [%d, %d) outside [0, 2)", row0, row0 + rows);
-  MMGT_CHECK(dtype == MMGT_F32 || dtype == MMGT_BF16, "accumulate_windows_weighted: bad dtype");
-  const long total = (long)rows * C * hw;
-  const dim3 grid((unsigned)((total + 255) / 256), (unsigned)F);
-  if (dtype == MMGT_BF16)
-    hipLaunchKernelGGL(accumulate_windows_weighted_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)pred, pred_sum, counter,
-                       idx, weights, B, Fw, F, C, Cpad, hw, rows, row0);
-  else
-    hipLaunchKernelGGL(accumulate_windows_weighted_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)pred, pred_sum, counter,
-                       idx, weights, B, Fw, F, C, Cpad, hw, rows, row0);
+                       weights, B, Fw, F, C, Cpad, hw, rows, row0);
   MMGT_LAUNCH_CHECK();
   return 0;
 }

@@ -100,8 +100,10 @@ _SIGS = {
     "mmgt_mask_to_latent": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_feather_alpha": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "mmgt_composite_u8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
-    "mmgt_accumulate_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+    "mmgt_accumulate_window": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p]),
+    "mmgt_accumulate_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int, c_void_p]),
     "mmgt_rotary": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
     "mmgt_film_residual": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p]),
     "mmgt_mean_tokens": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -167,13 +169,6 @@ _SIGS = {
     "mmgt_vp8dec_filter": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
     "mmgt_vp8dec_output": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "mmgt_accumulate_window_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
-                                            c_int, c_int, c_int, c_int, c_void_p]),
-    "mmgt_accumulate_windows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "mmgt_accumulate_window_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                c_int, c_int, c_void_p]),
-    "mmgt_accumulate_windows_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                                 c_int, c_int, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -1064,46 +1059,11 @@ def composite_u8(gen, orig, alpha, out=None):
     return out
 
 
-def accumulate_window(pred, pred_sum, counter, idx, C, rows=2, row0=0, bump_counter=True):
-    """pred ((rows*Fw), H, W, cpad) channels-last; pred_sum (2, C, F, H, W) fp32: CFG rows [row0, row0 + rows) += pred at
-    frames idx (int32 device); counter[idx] += 1 when bump_counter."""
-    _dev(pred, pred_sum, counter, idx)
-    assert idx.dtype == torch.int32 and pred.is_contiguous() and pred_sum.is_contiguous()
-    Fw = idx.numel()
-    F = pred_sum.shape[2]
-    hw = pred.shape[1] * pred.shape[2]
-    assert pred.shape[0] == rows * Fw and pred_sum.shape[0] == 2 and pred_sum.shape[3] * pred_sum.shape[4] == hw
-    if pred_sum.dtype != torch.float32 or counter.dtype != torch.float32:
-        raise RuntimeError(f"accumulate_window: pred_sum and counter must be float32, got {pred_sum.dtype} and {counter.dtype}")
-    if pred_sum.shape[1] != C:
-        raise RuntimeError(f"accumulate_window: pred_sum has {pred_sum.shape[1]} channels, C = {C}")
-    if counter.numel() != F or not counter.is_contiguous():
-        raise RuntimeError(f"accumulate_window: counter has {counter.numel()} entries for {F} frames")
-    _check(lib().mmgt_accumulate_window_rows(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), Fw, F, C, pred.shape[3],
-                                             hw, rows, row0, int(bump_counter), dtype_code(pred.dtype), _stream()),
-           "mmgt_accumulate_window_rows")
-
-
-def accumulate_windows(pred, pred_sum, counter, idx, C):
-    """The B windows of one sampler group in one launch: pred ((2*B*Fw), H, W, cpad) channels-last in CFG row major order [uncond w0 ..
-    uncond w(B-1), cond w0 .. cond w(B-1)], idx (B, Fw) int32 on the device.  Added window by window in list order, counter bumped once per
-    window: bitwise what B calls of `accumulate_window` on the windows' slices give."""
-    _dev(pred, pred_sum, counter, idx)
-    assert idx.dtype == torch.int32 and idx.dim() == 2 and idx.is_contiguous() and pred.is_contiguous() and pred_sum.is_contiguous()
-    B, Fw = idx.shape
-    F = pred_sum.shape[2]
-    hw = pred.shape[1] * pred.shape[2]
-    assert pred.shape[0] == 2 * B * Fw and pred_sum.shape[0] == 2 and pred_sum.shape[1] == C and pred_sum.shape[3] * pred_sum.shape[4] == hw
-    assert counter.numel() == F and counter.dtype == torch.float32 and pred_sum.dtype == torch.float32
-    _check(lib().mmgt_accumulate_windows(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), B, Fw, F, C, pred.shape[3], hw,
-                                         dtype_code(pred.dtype), _stream()), "mmgt_accumulate_windows")
-
-
-def _weighted_operands(what, pred, pred_sum, counter, idx, weights, C, B, Fw, rows, row0):
-    """The refusals shared by the two weighted accumulations, raised before anything is launched -> (F, hw)."""
+def _accumulate_operands(what, pred, pred_sum, counter, idx, weights, C, B, Fw, rows, row0):
+    """The refusals shared by the two window accumulations, raised before anything is launched -> (F, hw).  weights may be None."""
     _dev(pred, pred_sum, counter, idx, weights)
     if rows not in (1, 2) or row0 not in (0, 1) or row0 + rows > 2:
-        raise RuntimeError(f"{what}: rows must be 2 (row0 = 0), or 1 with row0 in (0, 1); got rows={rows}, row0={row0}")
+        raise RuntimeError(f"{what}: CFG rows: rows must be 2 (row0 = 0), or 1 with row0 in (0, 1); got rows={rows}, row0={row0}")
     if pred.dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"{what}: pred must be float32 or bfloat16, got {pred.dtype}")
     if idx.dtype != torch.int32 or not idx.is_contiguous():
@@ -1111,49 +1071,52 @@ def _weighted_operands(what, pred, pred_sum, counter, idx, weights, C, B, Fw, ro
     if pred.dim() != 4 or not pred.is_contiguous() or pred.shape[0] != rows * B * Fw or pred.shape[3] < C:
         raise RuntimeError(f"{what}: pred must be contiguous ({rows * B * Fw}, h, w, cpad >= {C}) for rows={rows}, {B} window(s) of {Fw} frames, "
                            f"got {tuple(pred.shape)}")
-    if pred_sum.dtype != torch.float32 or pred_sum.dim() != 5 or not pred_sum.is_contiguous() or pred_sum.shape[0] != 2 or pred_sum.shape[1] != C:
-        raise RuntimeError(f"{what}: pred_sum must be contiguous float32 (2, {C}, F, h, w), got {pred_sum.dtype} {tuple(pred_sum.shape)}")
+    if pred_sum.dtype != torch.float32 or counter.dtype != torch.float32:
+        raise RuntimeError(f"{what}: pred_sum must be float32 and counter must be float32, got {pred_sum.dtype} and {counter.dtype}")
+    if pred_sum.dim() != 5 or not pred_sum.is_contiguous() or pred_sum.shape[0] != 2 or pred_sum.shape[1] != C:
+        raise RuntimeError(f"{what}: pred_sum must be contiguous (2, C, F, h, w) with C = {C} channels, got {tuple(pred_sum.shape)}")
     F, hw = pred_sum.shape[2], pred.shape[1] * pred.shape[2]
     if pred_sum.shape[3] * pred_sum.shape[4] != hw:
         raise RuntimeError(f"{what}: pred has {hw} pixels per frame, pred_sum {pred_sum.shape[3] * pred_sum.shape[4]}")
-    if counter.dtype != torch.float32 or counter.numel() != F or not counter.is_contiguous():
-        raise RuntimeError(f"{what}: counter must be contiguous float32 with {F} entries, got {counter.dtype} with {counter.numel()}")
-    if weights.dtype != torch.float32 or tuple(weights.shape) != (Fw,) or not weights.is_contiguous():
+    if counter.numel() != F or not counter.is_contiguous():
+        raise RuntimeError(f"{what}: counter must be contiguous with one entry per frame: counter has {counter.numel()} entries for {F} frames")
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (Fw,) or not weights.is_contiguous()):
         raise RuntimeError(f"{what}: weights must be contiguous float32 ({Fw},), one per window position, got {weights.dtype} {tuple(weights.shape)}")
     if not 0 < Fw <= F:
         raise RuntimeError(f"{what}: a window of {Fw} frames in a clip of {F}")
     return F, hw
 
 
-def accumulate_window_weighted(pred, pred_sum, counter, idx, weights, C, rows=2, row0=0, bump_counter=True):
-    """`accumulate_window` with a weight per window position (include/mmgt_hip.h: mmgt_accumulate_window_weighted): pred_sum rows [row0, row0 + rows)
-    at frames idx = fmaf(weights[j], pred, pred_sum); counter[idx[j]] += weights[j] when bump_counter.  weights fp32 (Fw,) on the device."""
-    what = "accumulate_window_weighted"
+def accumulate_window(pred, pred_sum, counter, idx, C, rows=2, row0=0, bump_counter=True, weights=None):
+    """One window into the overlap average (include/mmgt_hip.h: mmgt_accumulate_window).  pred ((rows*Fw), h, w, cpad) channels-last; pred_sum
+    (2, C, F, h, w) fp32: CFG rows [row0, row0 + rows) at frames idx (int32 (Fw,) on the device) = fmaf(weights[j], pred, pred_sum);
+    counter[idx[j]] += weights[j] when bump_counter.  weights fp32 (Fw,) on the device, or None for 1 everywhere (the same bits as ones)."""
+    what = "accumulate_window"
     if idx.dim() != 1:
         raise RuntimeError(f"{what}: idx must be (Fw,), got {tuple(idx.shape)}")
     Fw = idx.numel()
     if Fw > 256:
         raise RuntimeError(f"{what}: a window of {Fw} frames (1 .. 256)")
-    F, hw = _weighted_operands(what, pred, pred_sum, counter, idx, weights, C, 1, Fw, rows, row0)
-    _check(lib().mmgt_accumulate_window_weighted(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), _ptr(weights), Fw, F, C, pred.shape[3], hw,
-                                                 rows, row0, int(bool(bump_counter)), dtype_code(pred.dtype), _stream()),
-           "mmgt_accumulate_window_weighted")
+    F, hw = _accumulate_operands(what, pred, pred_sum, counter, idx, weights, C, 1, Fw, rows, row0)
+    _check(lib().mmgt_accumulate_window(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), _ptr(weights), Fw, F, C, pred.shape[3], hw, rows, row0,
+                                        int(bool(bump_counter)), dtype_code(pred.dtype), _stream()), "mmgt_accumulate_window")
 
 
-def accumulate_windows_weighted(pred, pred_sum, counter, idx, weights, C, rows=2, row0=0):
-    """`accumulate_windows` with a weight per window position and for one or both CFG rows (include/mmgt_hip.h: mmgt_accumulate_windows_weighted):
-    pred ((rows*B*Fw), h, w, cpad) in CFG row major order, idx (B, Fw) int32.  Bitwise B calls of `accumulate_window_weighted` in list order."""
-    what = "accumulate_windows_weighted"
+def accumulate_windows(pred, pred_sum, counter, idx, C, rows=2, row0=0, weights=None):
+    """The B windows of one sampler group in one launch (include/mmgt_hip.h: mmgt_accumulate_windows): pred ((rows*B*Fw), h, w, cpad) channels-last
+    in CFG row major order [uncond w0 .. uncond w(B-1), cond w0 .. cond w(B-1)], idx (B, Fw) int32 on the device.  Added window by window in list
+    order, counter collecting every covering window's weight: bitwise what B calls of `accumulate_window` on the windows' slices give."""
+    what = "accumulate_windows"
     if idx.dim() != 2:
         raise RuntimeError(f"{what}: idx must be (B, Fw), got {tuple(idx.shape)}")
     B, Fw = idx.shape
     if not 1 <= B <= 256:
         raise RuntimeError(f"{what}: {B} windows in a group (1 .. 256)")
-    F, hw = _weighted_operands(what, pred, pred_sum, counter, idx, weights, C, B, Fw, rows, row0)
+    F, hw = _accumulate_operands(what, pred, pred_sum, counter, idx, weights, C, B, Fw, rows, row0)
     if F > 65535:
         raise RuntimeError(f"{what}: {F} frames (the launch has one grid row per frame, up to 65535)")
-    _check(lib().mmgt_accumulate_windows_weighted(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), _ptr(weights), B, Fw, F, C, pred.shape[3],
-                                                  hw, rows, row0, dtype_code(pred.dtype), _stream()), "mmgt_accumulate_windows_weighted")
+    _check(lib().mmgt_accumulate_windows(_ptr(pred), _ptr(pred_sum), _ptr(counter), _ptr(idx), _ptr(weights), B, Fw, F, C, pred.shape[3], hw, rows,
+                                         row0, dtype_code(pred.dtype), _stream()), "mmgt_accumulate_windows")
 
 
 # ------------------------------------------------------------------------------------------------------------ SMGA glue

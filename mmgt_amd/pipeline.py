@@ -329,12 +329,12 @@ class Pose2VideoPipeline:
 
         context_schedule="open", context_fuse and guidance_interval are opt-in; with none of them the loop makes the calls it always
         made.  context_fuse = "pyramid" / "ramp" weights the positions of a window in the overlap average (longclip.fuse_weights, rounded once to
-        fp32; hip.accumulate_window_weighted / accumulate_windows_weighted add fmaf(w, pred, sum) in list order and counter collects the weights, so
-        the update kernels divide by sum w unchanged); one window is always flat.  guidance_interval = (lo, hi) guides the steps with
+        fp32; hip.accumulate_window / accumulate_windows take it as `weights`, add fmaf(w, pred, sum) in list order and counter collects the weights,
+        so the update kernels divide by sum w unchanged); one window is always flat.  guidance_interval = (lo, hi) guides the steps with
         lo < (t + 1) / num_train_timesteps <= hi; on every other step ONLY the conditional row runs (cfg_row=1, with a memo of its own), its
         prediction goes to CFG row 1 and the update runs at guidance 1 over the zero row 0 -- v is the conditional average -- without the
-        rescale's moments.  Any given guidance_interval, (0, 1) included, and any fuse but "flat" route the accumulation through the weighted
-        entries (flat: all weights 1, the same bits).  Neither is combined with window_group: raises ValueError."""
+        rescale's moments.  Any given guidance_interval, (0, 1) included, and any fuse but "flat" hand the two entries a weight vector (flat: all
+        weights 1, the same bits as the `weights=None` of every other call).  Neither is combined with window_group: raises ValueError."""
         from .longclip import fuse_weights, step_is_guided
         eta, guidance_rescale, dpm, interval, B = self._check_loop_args(eta, guidance_rescale, window_group, context_fuse, guidance_interval,
                                                                         context_batch_size)
@@ -350,9 +350,8 @@ class Pose2VideoPipeline:
         nsteps = num_inference_steps or len(timesteps)
         # the reference passes step = 0 at every iteration, so the windows never move (:534-543)
         windows = list(sched(0, nsteps, video_length, context_frames, context_stride, context_overlap))
-        weighted = context_fuse != "flat" or guidance_interval is not None
         fuse_w = None
-        if weighted:                                             # one fp32 vector per clip; a lone window is averaged with nothing: flat
+        if context_fuse != "flat" or guidance_interval is not None:     # one fp32 vector per clip; a lone window is averaged with nothing: flat
             if len({len(c) for c in windows}) != 1:
                 raise RuntimeError("context_fuse / guidance_interval: the windows of a clip must have the same length")
             fuse_w = torch.tensor(fuse_weights(context_fuse if len(windows) > 1 else "flat", len(windows[0]), context_overlap),
@@ -400,15 +399,13 @@ class Pose2VideoPipeline:
         def accumulate(u, pred, pred_sum, counter):
             """One unit's prediction into pred_sum / counter.  The entry follows the call's options, not the unit's size (a lone last group is a group
             of one).  A single row goes to its own CFG row; of a cfg_split pair only row 0 bumps the counter, an unguided step's row 1 bumps it itself."""
-            rows, row0 = (2, 0) if u.row is None else (1, u.row)
-            if weighted and B > 1:
-                hip.accumulate_windows_weighted(pred, pred_sum, counter, u.idx, fuse_w, C, rows=rows, row0=row0)
-            elif weighted:
-                hip.accumulate_window_weighted(pred, pred_sum, counter, u.idx, fuse_w, C, rows=rows, row0=row0)
-            elif B > 1:
-                hip.accumulate_windows(pred, pred_sum, counter, u.idx, C)
+            kw = {} if u.row is None else dict(rows=1, row0=u.row)          # only what departs from the pair without weights: the defaults
+            if fuse_w is not None:                                          # make the calls they always made
+                kw["weights"] = fuse_w
+            if B > 1:
+                hip.accumulate_windows(pred, pred_sum, counter, u.idx, C, **kw)
             else:
-                hip.accumulate_window(pred, pred_sum, counter, u.idx, C, rows=rows, row0=row0, bump_counter=u.row in (None, 0))
+                hip.accumulate_window(pred, pred_sum, counter, u.idx, C, bump_counter=not (split and u.row == 1), **kw)
 
         def update(i, t, guided, pred_sum, counter):
             """Overlap average + CFG + the scheduler's update -> the next latents.  An unguided step: guidance 1 over the zero row 0 gives

@@ -38,7 +38,7 @@ CONV  (conv3x3: stride 1, 2, -2 = pad-high-only, upsample True and 2, two source
   Folded weights (packing.pack_conv3x3_up2: the taps that fall on one stored pixel summed in fp32 and rounded once; the [W_po W2 | W_po] image of
   unet3d `_ffpo_weights`): the CONTRACT multiplies the packed bf16 weights, as the kernel does.  `ideal` is the unfolded fp64 function; a relative
   error U on every folded weight moves it by at most  B_w = U sum |x||w_folded|,  gated as |out - ideal| <= 2 B + B_w  (B_s of attn_gate.py).
-  Tap gather (conv_out as a 36-column GEMM + elementwise.hip:295-315): Y[pixel][4 tap + o] is stored in bf16, the gather sums nine of them and the
+  Tap gather (conv_out as a 36-column GEMM + elementwise.hip:312-332): Y[pixel][4 tap + o] is stored in bf16, the gather sums nine of them and the
   bias in fp32 and rounds once.  The contract rounds the nine fp64 products to bf16; a product whose fp32 value lies across a rounding boundary from
   its fp64 value may round the other way, so B adds U sum_taps |y_tap| next to (320 + 4) u32 sum |x||w| and the ten fp32 additions.
 

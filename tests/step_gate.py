@@ -11,10 +11,11 @@ into an fma, so both forms are bounded.
 
 EXACT kernels (B = 0: the gate is torch.equal, `expected()` is what the kernel must store bit for bit)
   ncfhw_to_nhwc     elementwise.hip:44 one fp32 multiply, :48 / :51 the storage rounding  ==  (x * scale).to(dt) in fp32; pad channels 0 (:44).
-  accumulate_window(s)   elementwise.hip:120 one fp32 add per target and window, :152-157 the windows that hold a frame in list order  ==  the same
-                    adds by torch in that order; `accumulate_windows` == B sequential `accumulate_window` calls; a frame in no window is not
-                    written (:158 `if (any)`), its counter not either in the value (:161-164 adds nothing).  The counter: + 1.f per window.
-  qk_split3         elementwise.hip:233-235 sum = (qk0 + qk1) + bias in fp32, :237 hi = bf16(sum), :240 lo = bf16(sum - hi), :247-252 the pieces
+  accumulate_window(s)   without weights, elementwise.hip:130 one fmaf(1, v, s) = s + v per target and window, :169-174 the windows that hold a frame
+                    in list order  ==  the same adds by torch in that order; `accumulate_windows` == B sequential `accumulate_window` calls; a
+                    frame in no window is not written (:175 `if (any)`), its counter not either in the value (:178-181 adds nothing).  The
+                    counter: + 1.f per window.
+  qk_split3         elementwise.hip:250-252 sum = (qk0 + qk1) + bias in fp32, :254 hi = bf16(sum), :257 lo = bf16(sum - hi), :264-269 the pieces
                     [hi | hi | lo] of Qp and [hi | lo | hi] of Kp.
   gemm_bf16_f32 on integers in {-2 .. 2}: every partial sum is an integer of magnitude <= 4 K < 2^24, exact in fp32 in any order.
 
@@ -31,20 +32,20 @@ BOUNDED kernels
                     :103's product and fma); uncontracted fourteen.  Every one of the fourteen results contributes u32 of its magnitude, carried
                     through the linear steps behind it by the magnitudes of their coefficients (`CfgDdim.reference`): the contracted form
                     drops terms of this sum, so one B covers both.
-  softmax_rows / softmax_rows_f32_bf16   elementwise.hip:176-183, :196-216.  z = x scale.  The reference maximum cancels in the quotient, so only
-                    the ARGUMENT of every exponential matters: u32 |z| for the product (:177 / :201, absent in an fma), u32 |z - m| for the
+  softmax_rows / softmax_rows_f32_bf16   elementwise.hip:193-200, :213-233.  z = x scale.  The reference maximum cancels in the quotient, so only
+                    the ARGUMENT of every exponential matters: u32 |z| for the product (:194 / :218, absent in an fma), u32 |z - m| for the
                     difference, then `__expf` = v_exp_f32 (1 ulp) behind one multiply by log2 e (2 u32 |z - m|, as mm_gate states for SiLU):
                         eps_j = u32 (|z_j| + 3 |z_j - m| + 2)
-                    The sum: cols / 64 serial adds per lane (:180 / :209) + six shuffle adds (common.h:155-159) of positive terms: D u32,
-                    D = ceil(cols / 64) + 6, plus the terms' own errors sum_j p_j eps_j.  :182 one division (2 u32: a reciprocal of 1 ulp
-                    if not correctly rounded), :183 / :216 one product (u32), then the storage rounding (U |ref|, bf16).  An exponential or a
+                    The sum: cols / 64 serial adds per lane (:197 / :226) + six shuffle adds (common.h:155-159) of positive terms: D u32,
+                    D = ceil(cols / 64) + 6, plus the terms' own errors sum_j p_j eps_j.  :199 one division (2 u32: a reciprocal of 1 ulp
+                    if not correctly rounded), :200 / :233 one product (u32), then the storage rounding (U |ref|, bf16).  An exponential or a
                     probability below 2^-126 may be flushed: 2^-125 absolute.
                         B_j = p_j expm1(eps_j + sum_i p_i eps_i + (D + 3) u32) + U p_j (bf16) + 2^-125
   gemm_bf16_f32     gemm16.hip:720-737 raw fp32 accumulators of exact bf16 x bf16 products: (K + 2) u32 sum_k |a||w| (mm_gate LINEAR, no epilogue).
   logits chain      vae.py:267-275  t -> gemm_bf16_f32 with [Wq_hi; Wq_lo; Wk_hi; Wk_lo] -> qk_split3 -> gemm_bf16_f32, against the fp64
                     (t Wq^T + bq)(t Wk^T + bk)^T of the fp32 weights.  hi = bf16(x), lo = bf16(x - hi): |x - hi| <= U |x|, |x - hi - lo| <= U^2 |x| = 2^-16 |x|.
                         d_q = 2^-16 A_q + (C + 2) u32 A_q + 2 u32 (A_q + |bq|) + 2^-16 |q|,   A_q = sum_c |t_c||Wq_c|   (d_k likewise)
-                          (the weight pieces; the first GEMM's accumulation of the hi and lo columns; elementwise.hip:233 two adds; the split)
+                          (the weight pieces; the first GEMM's accumulation of the hi and lo columns; elementwise.hip:250 two adds; the split)
                         B = sum_c (d_q |k| + |q| d_k) + (2^-16 + (3 C + 2) u32 (1 + 2^-7)) sum_c |q_c||k_c|
                           (the dropped lo x lo term; the second GEMM's accumulation over 3 C exact products)
                     i.e. a few 2^-16 sum_c |q_c||k_c| at C = 512 (worst case; the pieces keep 16 bits at least, 17 on average).
@@ -502,7 +503,7 @@ class Softmax(_Case):
 # ---- the split-operand GEMM path --------------------------------------------------------------------------------------------------------------------
 
 def hi_lo(x):
-    """fp32 -> (hi, lo) bf16, hi = bf16(x), lo = bf16(x - hi) (vae.py:195-197, elementwise.hip:236-241)"""
+    """fp32 -> (hi, lo) bf16, hi = bf16(x), lo = bf16(x - hi) (vae.py:195-197, elementwise.hip:253-258)"""
     hi = x.to(BF16)
     return hi, (x - hi.float()).to(BF16)
 

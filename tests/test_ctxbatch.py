@@ -14,6 +14,7 @@ import torch
 
 from mmgt_amd.context import get_context_scheduler
 from mmgt_amd.scheduler import DDIMScheduler
+from tests import loop_doubles
 
 L, CTX, OV, STEPS, HW = 40, 12, 4, 4, 4
 
@@ -43,37 +44,10 @@ class _GroupUNet:
         return out
 
 
-def _install_cpu_doubles(monkeypatch, hip_mod):
-    """CPU restatements of the elementwise HIP ops of the loop; accumulate_windows restates include/mmgt_hip.h: window by window in list
-    order, counter bumped once per window."""
-    def accumulate_window(pred, pred_sum, counter, idx, C, rows=2, row0=0, bump_counter=True):
-        fw = idx.numel()
-        p5 = pred[..., :C].reshape(rows, fw, pred.shape[1], pred.shape[2], C).permute(0, 4, 1, 2, 3)
-        pred_sum[row0:row0 + rows, :, idx.long()] += p5
-        if bump_counter:
-            counter[idx.long()] += 1
-
-    def accumulate_windows(pred, pred_sum, counter, idx, C):
-        nb, fw = idx.shape
-        assert pred.shape[0] == 2 * nb * fw
-        p6 = pred[..., :C].reshape(2, nb, fw, pred.shape[1], pred.shape[2], C)
-        for k in range(nb):
-            pred_sum[:, :, idx[k].long()] += p6[:, k].permute(0, 4, 1, 2, 3)
-            counter[idx[k].long()] += 1
-
-    def cfg_ddim_step(pred_sum, counter, latents, g, sa_t, sb_t, sa_p, sb_p):
-        avg = pred_sum / counter.view(1, 1, -1, 1, 1)
-        v = avg[0:1] + g * (avg[1:2] - avg[0:1])
-        return sa_p * (sa_t * latents - sb_t * v) + sb_p * (sa_t * v + sb_t * latents)
-    monkeypatch.setattr(hip_mod, "accumulate_window", accumulate_window)
-    monkeypatch.setattr(hip_mod, "accumulate_windows", accumulate_windows, raising=False)
-    monkeypatch.setattr(hip_mod, "cfg_ddim_step", cfg_ddim_step)
-
-
 def _run(monkeypatch, batch, window_group=None):
     """(latents after every step, the double) of the L = 40, 12 / 4, 4-step run at context_batch_size = batch."""
     from mmgt_amd import pipeline as PL
-    _install_cpu_doubles(monkeypatch, PL.hip)
+    loop_doubles.install(monkeypatch, PL.hip)
     sched = DDIMScheduler()
     sched.set_timesteps(STEPS)
     unet = _GroupUNet()
@@ -180,7 +154,7 @@ def test_window_group_with_batched_windows_raises_the_documented_error():
 def test_accumulate_windows_restatement_equals_sequential_windows(monkeypatch):
     """The CPU restatement used above against B sequential accumulate_window calls on overlapping, wrapping lists: bitwise."""
     from mmgt_amd import pipeline as PL
-    _install_cpu_doubles(monkeypatch, PL.hip)
+    loop_doubles.install(monkeypatch, PL.hip)
     g = torch.Generator().manual_seed(3)
     F, fw, C = 20, 6, 4
     idx = torch.tensor([[0, 1, 2, 3, 4, 5], [3, 4, 5, 6, 7, 8], [17, 18, 19, 0, 1, 2]], dtype=torch.int32)

@@ -363,29 +363,11 @@ class _FakeWindowUNet:
         return out
 
 
-def _install_cpu_doubles(monkeypatch, hip_mod):
-    """CPU restatements of the two elementwise HIP ops the loop calls (pipeline_pose2vid_long.py:621-635), installed through
-    pytest's monkeypatch so that the real bindings are back for every later test of the session."""
-    def accumulate_window(pred, pred_sum, counter, idx, C, rows=2, row0=0, bump_counter=True):
-        fw = idx.numel()
-        p5 = pred[..., :C].reshape(rows, fw, pred.shape[1], pred.shape[2], C).permute(0, 4, 1, 2, 3)
-        pred_sum[row0:row0 + rows, :, idx.long()] += p5
-        if bump_counter:
-            counter[idx.long()] += 1
-
-    def cfg_ddim_step(pred_sum, counter, latents, g, sa_t, sb_t, sa_p, sb_p):
-        avg = pred_sum / counter.view(1, 1, -1, 1, 1)
-        v = avg[0:1] + g * (avg[1:2] - avg[0:1])
-        x0 = sa_t * latents - sb_t * v
-        eps = sa_t * v + sb_t * latents
-        return sa_p * x0 + sb_p * eps
-    monkeypatch.setattr(hip_mod, "accumulate_window", accumulate_window)
-    monkeypatch.setattr(hip_mod, "cfg_ddim_step", cfg_ddim_step)
-
-
 def _window_parallel_run(monkeypatch, window_group, L=40, ctx_frames=12, overlap=4, cfg_split="auto"):
+    """The loop over the CPU doubles of its elementwise HIP ops (tests/loop_doubles.py; pipeline_pose2vid_long.py:621-635)."""
     from mmgt_amd import pipeline as PL
-    _install_cpu_doubles(monkeypatch, PL.hip)
+    from tests import loop_doubles
+    loop_doubles.install(monkeypatch, PL.hip)
     sched = DDIMScheduler()
     sched.set_timesteps(4)
     pipe = PL.Pose2VideoPipeline(vae=None, image_encoder=None, reference_unet=None, denoising_unet=_FakeWindowUNet(),

@@ -1,12 +1,12 @@
 """The long-clip options of the sampler on the CPU: `context_schedule="open"`, `context_fuse`, `guidance_interval`.  The window lists,
 the weights and the guided steps are pure host arithmetic and are held to the values the definition gives; the loop runs over CPU doubles of the
-operator and of the elementwise HIP entries (tests/test_ctxbatch.py's, plus restatements of the two weighted accumulations)."""
+operator and of the elementwise HIP entries (tests/loop_doubles.py)."""
 import pytest
 import torch
 
 from mmgt_amd.scheduler import DDIMScheduler
 from tests import longclip_ref as LR
-from tests.test_ctxbatch import _install_cpu_doubles
+from tests import loop_doubles
 
 # ---- window lists -------------------------------------------------------------------------------------------------------------------------------------
 
@@ -142,35 +142,11 @@ class _RowUNet:
         return out
 
 
-def _install(monkeypatch, hip_mod):
-    """test_ctxbatch's doubles plus the two weighted accumulations restated from include/mmgt_hip.h: fmaf(w, pred, sum) window by window in list
-    order (torch.addcmul rounds the product first; with w = 1 it is the plain add either way), counter += w.  -> the call log."""
-    _install_cpu_doubles(monkeypatch, hip_mod)
-    log = []
-
-    def accumulate_window_weighted(pred, pred_sum, counter, idx, weights, C, rows=2, row0=0, bump_counter=True):
-        log.append(("window", rows, row0))
-        fw = idx.numel()
-        p5 = pred[..., :C].reshape(rows, fw, pred.shape[1], pred.shape[2], C).permute(0, 4, 1, 2, 3)
-        pred_sum[row0:row0 + rows, :, idx.long()] += weights.view(1, 1, fw, 1, 1) * p5
-        if bump_counter:
-            counter[idx.long()] += weights
-
-    def accumulate_windows_weighted(pred, pred_sum, counter, idx, weights, C, rows=2, row0=0):
-        log.append(("windows", rows, row0))
-        nb, fw = idx.shape
-        assert pred.shape[0] == rows * nb * fw
-        p6 = pred[..., :C].reshape(rows, nb, fw, pred.shape[1], pred.shape[2], C)
-        for k in range(nb):
-            pred_sum[row0:row0 + rows, :, idx[k].long()] += weights.view(1, 1, fw, 1, 1) * p6[:, k].permute(0, 4, 1, 2, 3)
-            counter[idx[k].long()] += weights
-    monkeypatch.setattr(hip_mod, "accumulate_window_weighted", accumulate_window_weighted, raising=False)
-    monkeypatch.setattr(hip_mod, "accumulate_windows_weighted", accumulate_windows_weighted, raising=False)
-    return log
+_install = loop_doubles.install
 
 
 def _run(monkeypatch, frames=L, **kw):
-    """-> (latents after every step, the double, the weighted entries' call log)"""
+    """-> (latents after every step, the double, the call log of the accumulations that were given weights: (form, rows, row0) each)"""
     from mmgt_amd import pipeline as PL
     own = monkeypatch is None
     mp = pytest.MonkeyPatch() if own else monkeypatch
@@ -188,7 +164,7 @@ def _run(monkeypatch, frames=L, **kw):
         traj = []
         pipe.denoise(lat, sched.timesteps, ehs, None, audio, masks, masks, masks, 3.5, None, context_frames=CTX, context_stride=1,
                      context_overlap=OV, num_inference_steps=STEPS, callback=lambda i, t, x: traj.append(x.clone()), **kw)
-        return traj, unet, log
+        return traj, unet, [entry[:3] for entry in log if entry[3]]
     finally:
         if own:
             mp.undo()

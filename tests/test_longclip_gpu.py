@@ -1,5 +1,5 @@
-"""The long-clip options of the sampler on the device: the two weighted window accumulations of csrc/elementwise.hip against fp64 and
-bit for bit against each other and against the unweighted entries; their refusals; the loop without weights over a stand-in whose prediction
+"""The long-clip options of the sampler on the device: the two window accumulations of csrc/elementwise.hip with weights against fp64 and
+bit for bit against each other, and with unit weights against weights=None; their refusals; the loop without weights over a stand-in whose prediction
 depends on the frame's position in its window; the real operator's steps restated from its own recorded predictions; the script flags.
 
 THE BOUNDS ARE DERIVED, NOT MEASURED (tests/longclip_ref.py states each next to the code that evaluates it).  u = 2^-24.
@@ -28,7 +28,7 @@ from tests.test_step_contract_gpu import guard_rows  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 F32, BF16 = torch.float32, torch.bfloat16
-WEIGHTED = ("mmgt_accumulate_window_weighted", "mmgt_accumulate_windows_weighted")
+ENTRIES = ("mmgt_accumulate_window", "mmgt_accumulate_windows")
 C, CPAD = 4, 64
 
 # ---- the kernels --------------------------------------------------------------------------------------------------------------------------------------
@@ -67,7 +67,7 @@ def _slice(pred, rows, B, Fw, k):
 @pytest.mark.parametrize("name", list(WINDOW_CASES))
 def test_weighted_accumulation_against_fp64(name, hw, dt, fuse, rows, row0):
     """the group launch and B single-window launches: each within the bound of the fp64 sum, and bit for bit each other; NaN behind every
-    operand; with rows = 1, row0 = 1 the unconditional row of pred_sum keeps its prefilled bits"""
+    operand; with rows = 1, row0 = 1 the unconditional row of pred_sum keeps its prefilled bits, and the same two hold with weights=None"""
     from mmgt_amd import hip
     F, wins, (h, w), pred, per_window, idx = _kernel_case("k", name, hw, dt, rows)
     B, Fw = idx.shape
@@ -77,14 +77,14 @@ def test_weighted_accumulation_against_fp64(name, hw, dt, fuse, rows, row0):
     if rows == 1:
         ps0[0] = G.rnd(f"longclip.row0.{name}.{hw}", (C, F, h, w), 1.0, device=DEV)
     ps_g, cnt_g = ps0.clone(), torch.zeros(F, device=DEV)
-    before = [hip.call_count(n) for n in WEIGHTED]
-    hip.accumulate_windows_weighted(G.guarded(pred, extra_rows=1), ps_g, cnt_g, guard_rows(idx), guard_rows(w32), C, rows=rows, row0=row0)
+    before = [hip.call_count(n) for n in ENTRIES]
+    hip.accumulate_windows(G.guarded(pred, extra_rows=1), ps_g, cnt_g, guard_rows(idx), C, rows=rows, row0=row0, weights=guard_rows(w32))
     ps_s, cnt_s = ps0.clone(), torch.zeros(F, device=DEV)
     for k in range(B):
-        hip.accumulate_window_weighted(G.guarded(_slice(pred, rows, B, Fw, k), extra_rows=1), ps_s, cnt_s, guard_rows(idx[k]), guard_rows(w32), C,
-                                       rows=rows, row0=row0)
+        hip.accumulate_window(G.guarded(_slice(pred, rows, B, Fw, k), extra_rows=1), ps_s, cnt_s, guard_rows(idx[k]), C, rows=rows, row0=row0,
+                              weights=guard_rows(w32))
     torch.cuda.synchronize()
-    assert [hip.call_count(n) - b for n, b in zip(WEIGHTED, before)] == [B, 1]
+    assert [hip.call_count(n) - b for n, b in zip(ENTRIES, before)] == [B, 1]
     for what, ps, cnt in (("group", ps_g, cnt_g), ("single", ps_s, cnt_s)):
         d = (ps[row0:row0 + rows].double() - S).abs()
         print(f"{what} {name} hw {hw} {fuse}: max |d| / B {(d / B_s.clamp_min(1e-300)).max().item():.3f}, counter |d| {(cnt.double() - W).abs().max().item():.2e}")
@@ -96,28 +96,36 @@ def test_weighted_accumulation_against_fp64(name, hw, dt, fuse, rows, row0):
             assert G.same_bits((ps[0], cnt), (ps0[0], cnt)), "CFG row 0 was written by a launch for row 1"
     assert G.same_bits((ps_g, cnt_g), (ps_s, cnt_s)), "the group launch differs from sequential single-window launches"
     assert S.abs().max() > 1 and W.min() > 0 and float(W.sum()) == pytest.approx(B * float(w32.double().sum()))     # every frame covered
+    if rows == 1:                                                # the same pair of launches with weights=None: a single row of the group form
+        ps_g, cnt_g, ps_s, cnt_s = ps0.clone(), torch.zeros(F, device=DEV), ps0.clone(), torch.zeros(F, device=DEV)
+        hip.accumulate_windows(G.guarded(pred, extra_rows=1), ps_g, cnt_g, guard_rows(idx), C, rows=rows, row0=row0)
+        for k in range(B):
+            hip.accumulate_window(G.guarded(_slice(pred, rows, B, Fw, k), extra_rows=1), ps_s, cnt_s, guard_rows(idx[k]), C, rows=rows, row0=row0)
+        assert G.same_bits((ps_g, cnt_g), (ps_s, cnt_s)), "weights=None: the group launch differs from sequential single-window launches"
+        assert G.same_bits((ps_g[0], cnt_g), (ps0[0], cnt_s)) and not torch.equal(ps_g[1], ps0[1]) and cnt_g.min() >= 1, "weights=None: CFG row 0 was written"
 
 
 @pytest.mark.parametrize("dt", [BF16, F32], ids=["bf16", "fp32"])
 @pytest.mark.parametrize("name", list(WINDOW_CASES))
 def test_unit_weights_are_bitwise_the_unweighted_entries(name, dt):
-    """on a prefilled pred_sum and counter: the group launch against accumulate_windows, the single launch against accumulate_window (both CFG rows,
-    and the conditional row alone)"""
+    """on a prefilled pred_sum and counter, weights of 1 against weights=None of the same entry: the group launch and the single launch, each for
+    both CFG rows and for either row alone"""
     from mmgt_amd import hip
     F, wins, (h, w), pred, _, idx = _kernel_case("unit", name, 15, dt, 2)
     B, Fw = idx.shape
     ones = torch.ones(Fw, device=DEV)
     ps0 = G.rnd(f"longclip.ps0.{name}", (2, C, F, h, w), 2.0, device=DEV)
     cnt0 = (torch.arange(F, device=DEV) % 3).to(F32)
-    a, ca, b, cb = ps0.clone(), cnt0.clone(), ps0.clone(), cnt0.clone()
-    hip.accumulate_windows_weighted(pred, a, ca, idx, ones, C)
-    hip.accumulate_windows(pred, b, cb, idx, C)
-    assert G.same_bits((a, ca), (b, cb)) and not torch.equal(a, ps0)
     for rows, row0 in ((2, 0), (1, 1), (1, 0)):
+        a, ca, b, cb = ps0.clone(), cnt0.clone(), ps0.clone(), cnt0.clone()
+        p = pred.view(2, B * Fw, h, w, CPAD)[row0:row0 + rows].reshape(rows * B * Fw, h, w, CPAD).contiguous()
+        hip.accumulate_windows(p, a, ca, idx, C, rows=rows, row0=row0, weights=ones)
+        hip.accumulate_windows(p, b, cb, idx, C, rows=rows, row0=row0)
+        assert G.same_bits((a, ca), (b, cb)) and not torch.equal(a, ps0), (rows, row0)
         a, ca, b, cb = ps0.clone(), cnt0.clone(), ps0.clone(), cnt0.clone()
         for k in range(B):
             p = _slice(pred, 2, B, Fw, k)[row0 * Fw:(row0 + rows) * Fw].contiguous()
-            hip.accumulate_window_weighted(p, a, ca, idx[k], ones, C, rows=rows, row0=row0, bump_counter=k != 1)
+            hip.accumulate_window(p, a, ca, idx[k], C, rows=rows, row0=row0, bump_counter=k != 1, weights=ones)
             hip.accumulate_window(p, b, cb, idx[k], C, rows=rows, row0=row0, bump_counter=k != 1)
         assert G.same_bits((a, ca), (b, cb)) and not torch.equal(a, ps0), (rows, row0)
 
@@ -129,8 +137,8 @@ def test_refusals_launch_nothing():
     w32 = LR.weights("pyramid", Fw).to(DEV)
     ps, cnt = torch.zeros((2, C, F, h, w), device=DEV), torch.zeros(F, device=DEV)
     one = _slice(pred, 2, B, Fw, 0)
-    group = lambda *a, **k: hip.accumulate_windows_weighted(*a, **k)
-    single = lambda *a, **k: hip.accumulate_window_weighted(*a, **k)
+    group = lambda p, ps, cnt, ix, w, C, **k: hip.accumulate_windows(p, ps, cnt, ix, C, weights=w, **k)
+    single = lambda p, ps, cnt, ix, w, C, **k: hip.accumulate_window(p, ps, cnt, ix, C, weights=w, **k)
     before = dict(hip._calls)
     for fn, p, ix in ((group, pred, idx), (single, one, idx[0].contiguous())):
         with pytest.raises(RuntimeError, match="pred must be float32 or bfloat16"):
@@ -245,15 +253,15 @@ def test_loop_open_pyramid_default_ddim():
     """the default update (cfg_ddim_step) behind the weighted accumulation; flat on the same windows gives other latents, by far more than the bounds"""
     from mmgt_amd import hip
     from mmgt_amd.scheduler import DDIMScheduler
-    before = {n: hip.call_count(n) for n in WEIGHTED + ("mmgt_cfg_ddim_step", "mmgt_sampler_step")}
+    before = {n: hip.call_count(n) for n in ENTRIES + ("mmgt_cfg_ddim_step", "mmgt_sampler_step")}
     out, unet = _denoise(DDIMScheduler(), context_schedule="open", context_fuse="pyramid")
-    assert hip.call_count(WEIGHTED[0]) - before[WEIGHTED[0]] == STEPS * 3 and hip.call_count(WEIGHTED[1]) == before[WEIGHTED[1]]
+    assert hip.call_count(ENTRIES[0]) - before[ENTRIES[0]] == STEPS * 3 and hip.call_count(ENTRIES[1]) == before[ENTRIES[1]]
     assert hip.call_count("mmgt_cfg_ddim_step") - before["mmgt_cfg_ddim_step"] == STEPS and hip.call_count("mmgt_sampler_step") == before["mmgt_sampler_step"]
     ref, bound = _reference("open", "pyramid", "cfg_ddim")
     _check(out, ref, bound, "denoise open + pyramid, ddim")
     two, u2 = _denoise(DDIMScheduler(), context_schedule="open", context_fuse="pyramid", context_batch_size=2)
     assert torch.equal(out, two) and len(u2.calls) == STEPS * 2 and len(unet.calls) == STEPS * 3
-    assert hip.call_count(WEIGHTED[1]) - before[WEIGHTED[1]] == STEPS * 2
+    assert hip.call_count(ENTRIES[1]) - before[ENTRIES[1]] == STEPS * 2
     # the fuse must matter on this stand-in, or the test shows nothing
     ref_f, bound_f = _reference("open", "flat", "cfg_ddim")
     assert ((ref - ref_f).abs() > 2 * (bound + bound_f)).any() and (ref - ref_f).abs().max() > 1e-2
@@ -295,14 +303,26 @@ def test_loop_uniform_pyramid_interval_rescale(eta):
     assert u2.calls == [(t, 4 if f else 2, None if f else 1) for t, f in zip(R.trailing_timesteps(STEPS), flags) for _ in range(2)]
 
 
-def test_loop_defaults_touch_none_of_the_new_entries():
+def test_loop_defaults_touch_none_of_the_new_entries(monkeypatch):
+    """the defaults hand the two accumulations no weight vector (the weighted path is an operand now, not an entry of its own)"""
     from mmgt_amd import hip
     from mmgt_amd.scheduler import DDIMScheduler
-    before = [hip.call_count(n) for n in WEIGHTED]
+    given = []
+
+    def recording(name, real):
+        def fn(*a, weights=None, **k):
+            given.append((name, weights is not None))
+            return real(*a, weights=weights, **k)
+        return fn
+    for name in ("accumulate_window", "accumulate_windows"):
+        monkeypatch.setattr(hip, name, recording(name, getattr(hip, name)))
+    before = [hip.call_count(n) for n in ENTRIES]
     for kw in ({}, dict(context_batch_size=2), dict(context_schedule="open")):
         out, unet = _denoise(DDIMScheduler(), **kw)
         assert torch.isfinite(out).all() and all(cfg_row is None for _, _, cfg_row in unet.calls)
-    assert [hip.call_count(n) for n in WEIGHTED] == before
+    assert [hip.call_count(n) - b for n, b in zip(ENTRIES, before)] == [STEPS * (4 + 3), STEPS * 2]
+    assert len(given) == STEPS * (4 + 3 + 2) and {name for name, _ in given} == {"accumulate_window", "accumulate_windows"}
+    assert not any(weighted for _, weighted in given)
 
 
 # ---- the real operator --------------------------------------------------------------------------------------------------------------------------------

@@ -207,8 +207,8 @@ class _UNet:
 def _run(monkeypatch, scheduler, **kw):
     """-> (calls of cfg_ddim_step, calls of sampler_step, final latents) of a 5-step run over the doubles"""
     from mmgt_amd import pipeline as PL
-    from tests.test_ctxbatch import _install_cpu_doubles
-    _install_cpu_doubles(monkeypatch, PL.hip)
+    from tests import loop_doubles
+    loop_doubles.install(monkeypatch, PL.hip)
     old, new = [], []
     ddim = PL.hip.cfg_ddim_step
 

@@ -209,7 +209,7 @@ def test_accumulate_window_refusals():
     c = G.acc_case("gpu.acc.ref", [[0, 1, 2, 3]], 6, 4, 8, 3, 3, BF16, DEV)
     pred, idx = c.window_pred(0), torch.tensor(c.windows[0], device=DEV, dtype=torch.int32)
     ps, cnt = c.ps0.clone(), c.cnt0.clone()
-    before = hip.call_count("mmgt_accumulate_window_rows")
+    before = hip.call_count("mmgt_accumulate_window")
     with pytest.raises(RuntimeError, match="must be float32"):
         hip.accumulate_window(pred, ps.double(), cnt, idx, 4)
     with pytest.raises(RuntimeError, match="must be float32"):
@@ -218,7 +218,7 @@ def test_accumulate_window_refusals():
         hip.accumulate_window(pred, ps, cnt, idx, 3)
     with pytest.raises(RuntimeError, match="counter has"):
         hip.accumulate_window(pred, ps, cnt[:5].contiguous(), idx, 4)
-    assert hip.call_count("mmgt_accumulate_window_rows") == before
+    assert hip.call_count("mmgt_accumulate_window") == before
     assert torch.equal(ps, c.ps0) and torch.equal(cnt, c.cnt0)
 
 

@@ -4,10 +4,10 @@
 bf16, guidance 3.5, random-init weights of the reference architecture, `Pose2VideoPipeline.denoise` alone between HIP events, every comparison in
 alternating pairs in ONE process on the same box (`--pairs`, at least five) after a warm-up of both sides.  Three kinds of line:
 
-  * "accumulate": us per launch of mmgt_accumulate_windows_weighted beside mmgt_accumulate_windows at B = 4, Fw = 12, 64 x 64 latents, C = 4,
-    Cpad = 64 (bf16 predictions, open windows of a 36-frame clip), `--launches` launches per sample;
+  * "accumulate": us per launch of mmgt_accumulate_windows with a weight vector beside the same entry without one at B = 4, Fw = 12, 64 x 64
+    latents, C = 4, Cpad = 64 (bf16 predictions, open windows of a 36-frame clip), `--launches` launches per sample;
   * "forward": ms per step of a step that runs the CFG pair beside a step that runs the conditional row alone -- 512 x 512 x 24 in one window, and
-    512 x 512 x 80 at windows of 12 / 4 with context_batch_size 1 and 4.  Both sides go through the weighted entries (guidance_interval = (0, 1)
+    512 x 512 x 80 at windows of 12 / 4 with context_batch_size 1 and 4.  Both sides hand the entries a weight vector (guidance_interval = (0, 1)
     against an interval that holds no step), so only the forward and the skipped row differ;
   * "clip": ms per 80-frame clip at 25 steps, uniform / flat / every step guided (the defaults) beside open / pyramid / guidance_interval
     (0.25, 0.75).
@@ -68,7 +68,7 @@ def bench_accumulate(a, dev):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / a.launches
     flat = lambda: hip.accumulate_windows(pred, ps, cnt, idx, C)
-    weighted = lambda: hip.accumulate_windows_weighted(pred, ps, cnt, idx, w, C)
+    weighted = lambda: hip.accumulate_windows(pred, ps, cnt, idx, C, weights=w)
     us(flat), us(weighted)
     rec = {"kind": "accumulate", "B": B, "Fw": Fw, "F": F, "C": C, "Cpad": cpad, "latent": [hw, hw], "pred": "bf16", "launches_per_sample": a.launches,
            "bytes_read_pred": pred.numel() * 2, "box": torch.cuda.get_device_name(0)}
