@@ -736,175 +736,75 @@ int launch_cfg(const ADesc& ad, const void* W, long bsw, const Epi& ep, int M, i
   return 0;
 }
 
-int g_splitk = 1;     // mmgt_tune("splitk", 0 / 1): A/B switch of the split-K path
-int g_tailsplit = 1;  // mmgt_tune("tailsplit", 0 / 1): A/B switch of the tail split (below)
-int g_gemm_cfg = 0;   // 0 = heuristic; 1, 3, 6, 9, 12, 16, 17, 19, 20 force a tile configuration (mmgt_tune("gemm_cfg", v), benchmarking only)
-int g_bm192 = 1;      // mmgt_tune("bm192", 0 / 1): A/B switch of the 192-row gemm16 tile
-
 }  // namespace
-// gemm16.hip: the bf16 256x256 8-phase core on 16x16x32 MFMAs (cfg 16)
-int mmgt_gemm16_launch(int mode, int bn, const void* ad, const void* W, long bsw, const void* ep, int M, int N, int K,
+#include "gemm_plan.h"   // shape -> plan: which of the launches below a GEMM / conv gets
+// gemm16.hip: the bf16 256x256 8-phase core on 16x16x32 MFMAs (bm x bn tiles: 256 x 128 / 256 / 320, 192 x 320)
+int mmgt_gemm16_launch(int mode, int bm, int bn, const void* ad, const void* W, long bsw, const void* ep, int M, int N, int K,
                        int batch, void* stream);
 int mmgt_gemm16_splitk(int mode, int bn, const void* ad, const void* W, const void* ep, int M, int N, int K, int S, void* stream, int m0);
 namespace {
 
+mmgt_plan::GemmSwitches g_sw;   // the A/B switches of the plan (mmgt_tune: gemm_cfg, splitk, tailsplit, bm192)
+
+template <typename T, int MODE, int TILE>
+int launch_tile(const ADesc& ad, const void* W, long bsw, const Epi& ep, int M, int N, int K, int batch, hipStream_t s) {
+  constexpr mmgt_plan::TileDims d = mmgt_plan::TILE_DIMS[TILE];
+  return launch_cfg<T, MODE, d.BM, d.BN, d.WM, d.WN, d.NSTAGE, 128, d.EPI>(ad, W, bsw, ep, M, N, K, batch, s);
+}
+
+// The tail split of a conv (gemm_plan.h): images [0, rows_a / (OH * OW)) as one launch, the rest with the reduction split in two.
+template <typename T>
+int launch_tail_split(int bn, int rows_a, const ADesc& ad, const void* W, long bsw, const Epi& ep, int M, int N, int K, hipStream_t s) {
+  int rc = mmgt_gemm16_launch(1, 256, bn, &ad, W, bsw, &ep, rows_a, N, K, 1, s);
+  if (rc) return rc;
+  ADesc adb = ad;
+  Epi epb = ep;
+  const long esz = sizeof(T), n0 = rows_a / ((long)ad.OH * ad.OW);
+  adb.src0 = ad.src0 + n0 * ad.IH * ad.IW * ad.C0 * esz;
+  if (ad.src1) adb.src1 = ad.src1 + n0 * ad.IH * ad.IW * ad.C1 * esz;
+  if (ep.residual) epb.residual = ep.residual + (long)rows_a * ep.ldr * esz;
+  epb.out = ep.out + (long)rows_a * ep.ldo * esz;
+  return mmgt_gemm16_splitk(1, bn, &adb, W, &epb, M - rows_a, N, K, 2, s, rows_a);
+}
+
+// shape -> plan (gemm_plan.h decides) -> launch
 template <typename T, int MODE>
 int launch(const ADesc& ad, const void* W, long bsw, const Epi& ep, int M, int N, int K, int batch, hipStream_t s) {
-  const bool geglu = ep.act == 1;
-  int cfg = g_gemm_cfg;
-  // Split-K (gemm16.hip): a long reduction on a grid of at most half a tile per CU -- the 8x8-level convs (3072 rows x 1280 columns,
-  // K = 11 520 / 23 040) and ff2 of that level (K = 5120).  S slices with >= 16 chunks of 64 each, S x tiles <= 256.
-  if ((cfg == 0 || cfg == 18) && g_splitk && std::is_same<T, bf16_t>::value && batch == 1 && ep.act == 0 && ep.fast && !ep.row_scale &&
-      ep.alpha == 1.f && !ep.bias_post && N % 8 == 0 && K >= 2560 && (N % 256 == 0 || N % 320 == 0) &&
-      (((uintptr_t)ep.bias | (uintptr_t)ep.bias2) & 15) == 0) {
-    const int bn = N % 256 == 0 ? 256 : 320;
-    const long tiles = (long)((M + 255) / 256) * (N / bn);
-    const int nch = K / 64;
-    int S = 0;
-    // (measured, tools/ab_cfg.py SET=ctx12 / step: at <= 64 tiles slices of >= 16 chunks pay -- 8x8 convs 126 -> 71 us, 248 -> 101 us, ff2
-    // 59 -> 47 us at 12 frames --; between 65 and 128 tiles only long slices do: the 16x16 convs of a 12-frame window -5 %, their ff2 +10 %)
-    for (int c = 8; c >= 2; --c)
-      if (tiles * c <= 256 && nch % c == 0 && nch / c >= (tiles <= 64 ? 16 : 64)) { S = c; break; }
-    // (dense shapes between 33 and 64 tiles -- ff2 of the 8x8 level at 24 frames, 3072 x 1280 x 5120 -- run 8 % faster on the 128 x 64 tile
-    //  than split four ways: 58.1 against 63.0 us, profiles/r5/ab_cfg_deep_r5.txt; the convs of that level keep the split: 126 -> 71 us)
-    if (S >= 2 && tiles <= 128 && (MODE == 1 || tiles <= 32 || tiles > 64)) return mmgt_gemm16_splitk(MODE, bn, &ad, W, &ep, M, N, K, S, s, 0);
-  }
-  if (cfg == 18) cfg = 0;
-  if (cfg == 0) {
-    // Measured on MI355X with tools/ab_gemm.py / tools/bench_kernels.py (one process, one device; re-swept after the
-    // LDS-DMA moved to buffer addressing, which made 128x128 the better small tile for every dense shape):
-    //   cfg 6  (256x128, 8 waves, 3-deep ring)    long reductions, GEGLU, and the widest L0 projections;
-    //   cfg 1  (128x128, 2 workgroups / CU)       every other dense shape, and the conv gather on the small levels;
-    //   cfg 12 (128x320, 8 waves, barrier inside the chunk)   conv outputs whose width is a multiple of 320 on the two
-    //          large levels: the im2col gather is staged once per 320 columns instead of once per 128 (-5..-20%);
-    //   cfg 3  (128x64, 3 workgroups / CU)        conv grids that would not fill the chip (the 8x8 level).
-    const long tiles128 = (long)((M + 127) / 128) * ((N + 127) / 128) * batch;
-    const long tiles256 = (long)((M + 255) / 256) * ((N + 127) / 128) * batch;
-    //   cfg 9  (256x256, 8 waves, 2-deep ring, barrier inside the chunk)   long reductions whose grid still gives ~one tile
-    //          per CU: the 16x16-level convs (-6%); dense shapes: below.
-    const long tiles256sq = (long)((M + 255) / 256) * ((N + 255) / 256) * batch;
-    const bool big_ok = N % 256 == 0 && K >= 2560 && tiles256sq >= 192 && tiles256sq <= 512;
-    // dense: the 256x256 tile wherever N fills its columns to within 7% (N = 960, 1280, 1920, 2560, 3840, 5120, 10240) and
-    // the grid still covers the chip -- with the slim common epilogue it no longer spills: GEGLU ff1 -11..-13%, q/k/v
-    // projections of the motion modules -13%, the N = 1280 family -5..-10%.
-    // (and M: the batched W.X^T projections have M = 320 / 640 rows per problem, 62 / 83 % of two / three 256-row tiles: -13..-17 % on the 128x128 tile)
-    const bool sq_ok = ((N + 255) / 256) * 256l * 100 <= (long)N * 107 && ((M + 255) / 256) * 256l * 100 <= (long)M * 115 && tiles256sq >= 192;
-    // cfg 16 (gemm16.hip: 256x256, 16x16x32 MFMAs, two wave groups in ping-pong; bf16 only) replaces cfg 9 wherever that ran and
-    // takes the convs whose width fills 256-column tiles: measured (tools/ab_cfg.py, one process) -17..-19% on the 16x16-level
-    // convs and the 16 -> 32 up-conv, -7..-10% on the long-K / wide dense shapes, -7% on the 32 -> 64 up-conv (N = 640: three
-    // tiles with 17% padding still beat the 128x320 tile); K = 320 GEGLU too since the two wave groups run their epilogues side by
-    // side (-9%); it loses on N = 320 / 640.
-    // cfg 17 = the same core with a 256x320 tile (every width of the UNet is a multiple of 320): the L0 / L1 convs and the
-    // 32 -> 64 / 16 -> 32 up-convs (-2..-22%), the dense N = 320 / 640 / 960 shapes of the 64x64 level (-6..-27%) and the long-K,
-    // residual or N = 1280 shapes of the 32x32 level (-5..-8%).
-    const bool b16 = std::is_same<T, bf16_t>::value;
-    if (MODE == 1) {
-      if (b16 && N % 320 == 0 && (M >= 49152 || (M >= 24576 && N >= 640))) cfg = 17;   // (12-frame windows: the 32x32-level convs, -7..-9 % against 128x128)
-      else if (b16 && N % 256 == 0 && tiles256sq >= 192) cfg = 16;
-      else cfg = (N % 320 == 0 && M >= 49152) ? 12 : big_ok ? 9 : (tiles128 < 512 || N <= 64) ? 3 : 1;   // (N <= 64: conv_out's 3 / 4 channels padded
-                                                                                                         //  to 64 -- VAE 8 x 512^2 x 128 -> 64: 651 -> 503 us on the 128x64 tile)
-    } else if (b16 && !geglu && N % 320 == 0 && N <= 960 && M >= 131072) cfg = 17;
-    else if (b16 && !geglu && N % 320 == 0 && N <= 1280 && M >= 49152 && (K >= 1280 || ep.residual || N == 1280)) cfg = 17;   // 32x32 level
-    else if (b16 && !geglu && N == 640 && M >= 24576 && K >= 2560 && g_bm192) cfg = 17;   // (12-frame windows: ff2 of the 32x32 level on the 192-row tile, 90.4 -> 82.3 us)
-    else if (sq_ok) cfg = b16 ? 16 : 9;
-    else if (geglu || K >= 1280) cfg = tiles256 >= 256 ? 6 : (!geglu && tiles128 <= 256) ? 3 : 1;   // (<= one 128x128 tile per CU: 128x64 tiles, -5..-7 % at M = 3072)
-    else if (M >= 131072 && N >= 640) cfg = 6;
-    else cfg = 1;
-  }
-  if (geglu && (cfg == 3 || cfg == 12)) cfg = 1;   // GEGLU pairs need 64-column wave tiles
-  if (MODE == 1 && ad.up >= 2 && cfg != 16 && cfg != 17) cfg = N % 320 == 0 ? 17 : 16;   // the four-phase upsample conv exists in gemm16.hip only
-  // cfg 19 = gemm16's 192 x 320 tile (round 5): taken where 256-row tiles leave the last round of the persistent grid half empty.  With T
-  // tiles on 256 CUs a launch runs ceil(T / 256) rounds of one tile time; a 192-row tile takes ~0.88 of a 256-row tile's time (three MFMA row
-  // tiles per four W fragment reads instead of four).  Measured (tools/ab_cfg.py SET=bm192, profiles/r5/ab_cfg_bm192_r5.txt): 49 152 x 640
-  // (384 tiles = 2 rounds against 512 = 2 x 0.88): K = 640 + residual 66.1 -> 62.5 us, K = 2560 + residual 184.8 -> 170.6, K = 1280 89.9 ->
-  // 83.2; conv 32 x 32, 320 -> 640 185 -> 174; 12-frame windows: 98 304 x 320 + residual 50.3 -> 46.2, 24 576 x 640 x 2560 88.4 -> 82.3, convs
-  // 175 -> 167 and 190 -> 178.  It loses where the round count does not drop (196 608 rows, N = 1280) and against the tail split of the
-  // long-reduction convs (48 x 32 x 32, 640 -> 640: 305 us against 322), which therefore keeps its shapes.
-  bool bm192 = cfg == 19;
-  if (cfg == 19) cfg = 17;
-  if (cfg == 17 && !bm192 && g_gemm_cfg == 0 && g_bm192 && std::is_same<T, bf16_t>::value && batch == 1 && N % 320 == 0) {
-    const long tn = N / 320;
-    const long r256 = (((long)(M + 255) / 256) * tn + 255) / 256, r192 = (((long)(M + 191) / 192) * tn + 255) / 256;
-    bm192 = (double)r192 * 0.88 < (double)r256 * 0.97;
-  }
-  if (cfg == 16 || cfg == 17) {   // gemm16.hip, 256 / 320 columns: bf16, plain vectorised epilogue only (GEGLU: 256); else fall back
-    const bool post = ep.row_scale || ep.alpha != 1.f || ep.bias_post;   // row scale / alpha / post-scale bias: without GEGLU only
-    if (std::is_same<T, bf16_t>::value && ep.fast && ep.act <= (cfg == 16 && !post ? 1 : 0) &&
-        (((uintptr_t)ep.bias | (uintptr_t)ep.bias2 | (uintptr_t)ep.bias_post) & 15) == 0 && N % 4 == 0) {   // (bias vectors travel by 16-byte DMA)
-      const int bn = cfg == 16 ? 256 : bm192 ? 192320 : 320;   // (192320: the 192 x 320 tile)
-      // Tail split.  A persistent grid of T tiles runs ceil(T / 256) rounds of one tile per CU; with a long reduction and T = 256 q + r,
-      // r <= 128 (the 32x32 level: 49 152 rows x 640 columns = 384 tiles), the last round keeps half the chip idle for a whole tile.  The
-      // rows of the r tail tiles run as a second launch with the reduction split in two (2 r <= 256 half-tiles: one round of half the
-      // length) + the fixed-order reduce.  Convs only (reductions of 2880 .. 17 280: 32x32 convs 640 -> 640 338 -> 310 us, 1280 -> 640
-      // 631 -> 556, 1920 -> 640 923 -> 791): the fp32 partial slabs and the reduce cost ~25 us, which a dense K = 2560 tile does not repay.
-      const int bnc = cfg == 16 ? 256 : 320;
-      const long tiles_n = (N + bnc - 1) / bnc, tiles_m = (M + 255) / 256, ntile = tiles_m * tiles_n;
-      const int nch = K / 64;
-      if (g_tailsplit && (!bm192 || g_gemm_cfg == 0) && MODE == 1 && batch == 1 && !ad.ksplit && ep.act == 0 && !post && N % bnc == 0 && N % 8 == 0 && K >= 2560 && nch % 2 == 0 && ntile > 256) {
-        const long rows_a = (256 * (ntile / 256) / tiles_n) * 256;                  // whole row tiles that fill ntile / 256 full rounds
-        const long tail = (tiles_m - rows_a / 256) * tiles_n;
-        const long img = MODE == 1 ? (long)ad.OH * ad.OW : 1;
-        if (rows_a > 0 && rows_a < M && tail > 0 && 2 * tail <= 256 && 4 * tail >= 256 && rows_a % img == 0) {
-          int rc = mmgt_gemm16_launch(MODE, bnc, &ad, W, bsw, &ep, (int)rows_a, N, K, 1, s);
-          if (rc) return rc;
-          ADesc adb = ad;
-          Epi epb = ep;
-          const long esz = sizeof(T);
-          if (MODE == 1) {
-            const long n0 = rows_a / img;
-            adb.src0 = ad.src0 + n0 * ad.IH * ad.IW * ad.C0 * esz;
-            if (ad.src1) adb.src1 = ad.src1 + n0 * ad.IH * ad.IW * ad.C1 * esz;
-          } else {
-            adb.src0 = ad.src0 + rows_a * ad.ld0 * esz;
-          }
-          if (ep.residual) epb.residual = ep.residual + rows_a * ep.ldr * esz;
-          epb.out = ep.out + rows_a * ep.ldo * esz;
-          return mmgt_gemm16_splitk(MODE, bnc, &adb, W, &epb, (int)(M - rows_a), N, K, 2, s, (int)rows_a);
-        }
-      }
-      return mmgt_gemm16_launch(MODE, bn, &ad, W, bsw, &ep, M, N, K, batch, s);
-    }
-    if (MODE == 1 && ad.up >= 2) {
+  using namespace mmgt_plan;
+  GemmShape sh{};
+  sh.bf16 = std::is_same<T, bf16_t>::value;
+  sh.mode = MODE;
+  sh.M = M; sh.N = N; sh.K = K; sh.batch = batch;
+  sh.act = ep.act;
+  sh.fast = ep.fast != 0;
+  sh.post = ep.row_scale || ep.alpha != 1.f || ep.bias_post;
+  sh.residual = ep.residual != nullptr;
+  sh.bias_unaligned = (((uintptr_t)ep.bias | (uintptr_t)ep.bias2) & 15) != 0;
+  sh.bias_post_unaligned = (((uintptr_t)ep.bias | (uintptr_t)ep.bias2 | (uintptr_t)ep.bias_post) & 15) != 0;
+  sh.up = ad.up;
+  sh.ksplit = ad.ksplit;
+  sh.img = MODE == 1 ? (long)ad.OH * ad.OW : 1;
+  const GemmPlan p = plan_gemm(sh, g_sw);
+  switch (p.kind) {
+    case PLAN_G16_TILE: return mmgt_gemm16_launch(MODE, p.bm, p.bn, &ad, W, bsw, &ep, M, N, K, batch, s);
+    case PLAN_G16_SPLITK: return mmgt_gemm16_splitk(MODE, p.bn, &ad, W, &ep, M, N, K, p.S, s, 0);
+    case PLAN_G16_TAIL: return launch_tail_split<T>(p.bn, p.rows_a, ad, W, bsw, ep, M, N, K, s);
+    case PLAN_REFUSE:
       mmgt_set_error("conv: the four-phase upsample form and the two-source 1 x 1 conv need the gemm16 path (bf16, 16-byte aligned bias, Cout %% 4 == 0)");
       return 1;
-    }
-    cfg = cfg == 16 ? 9 : geglu ? 1 : 12;   // (GEGLU pairs need 64-column wave tiles: not the 320-column tile)
+    case PLAN_TILE: break;
   }
-  if (cfg == 20) {   // gemm16.hip's 256 x 128 tile (round 5): the VAE's 128-wide levels
-    if (std::is_same<T, bf16_t>::value && ep.fast && ep.act == 0 && (((uintptr_t)ep.bias | (uintptr_t)ep.bias2 | (uintptr_t)ep.bias_post) & 15) == 0 && N % 4 == 0)
-      return mmgt_gemm16_launch(MODE, 128, &ad, W, bsw, &ep, M, N, K, batch, s);
-    cfg = 1;
+  switch (p.tile) {
+    case T128x64: return launch_tile<T, MODE, T128x64>(ad, W, bsw, ep, M, N, K, batch, s);
+    case T256x128: return launch_tile<T, MODE, T256x128>(ad, W, bsw, ep, M, N, K, batch, s);
+    case T256x256: return launch_tile<T, MODE, T256x256>(ad, W, bsw, ep, M, N, K, batch, s);
+    case T128x320: return launch_tile<T, MODE, T128x320>(ad, W, bsw, ep, M, N, K, batch, s);
+    case T128x128_POST:   // (dense only: a conv with row scale / alpha / post-scale bias is planned FULL)
+      if constexpr (MODE == 0) return launch_tile<T, MODE, T128x128_POST>(ad, W, bsw, ep, M, N, K, batch, s);
+      [[fallthrough]];
+    case T128x128_FULL: return launch_tile<T, MODE, T128x128_FULL>(ad, W, bsw, ep, M, N, K, batch, s);
+    default: return launch_tile<T, MODE, T128x128>(ad, W, bsw, ep, M, N, K, batch, s);
   }
-  // anything beyond bias / per-batch bias / GEGLU / residual on the vectorised path runs the FULL instantiation (128x128 tile)
-  if (!ep.fast || ep.act >= 2) return launch_cfg<T, MODE, 128, 128, 2, 2, 2, 128, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-  if (ep.row_scale || ep.alpha != 1.f || ep.bias_post) {
-    if (MODE == 0 && !geglu) return launch_cfg<T, 0, 128, 128, 2, 2, 2, 128, 1>(ad, W, bsw, ep, M, N, K, batch, s);
-    return launch_cfg<T, MODE, 128, 128, 2, 2, 2, 128, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-  }
-#ifdef MMGT_GEMM_AB   // A/B builds (make ab) instantiate only the production tiles: seconds instead of minutes
-  switch (cfg) {
-    case 3: return launch_cfg<T, MODE, 128, 64, 2, 2, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-    case 6: return launch_cfg<T, MODE, 256, 128, 4, 2, 3>(ad, W, bsw, ep, M, N, K, batch, s);
-    case 9: return launch_cfg<T, MODE, 256, 256, 2, 4, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-    case 12: return launch_cfg<T, MODE, 128, 320, 4, 2, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-    default: return launch_cfg<T, MODE, 128, 128, 2, 2, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-  }
-#else
-  // Tiles measured and dropped (tools/ab_gemm.py, one process, one device): 128x128 / 128x64 with a 3-deep ring (round 5 again, with 4-deep
-  // rings too, on the M = 1536 / 3072 shapes of the 8x8 level: profiles/r5/ab_cfg_deep_r5.txt -- 128x64 x 3 gains 10 % at M = 1536 only), 64x64,
-  // 256x128 with a 2-deep ring, 256x64, 256x256 with a 3- or 4-deep ring of 64-byte rows, 256x320 on 8 waves (accumulators +
-  // double-buffered fragments spill inside the main loop; with single-buffered W fragments reloaded right after their last
-  // MFMA it still spills 56-139 VGPRs and runs 1179 us at 8192^3 against 965) and 256x256 / 256x320 on 4 waves (one wave per SIMD, 512
-  // registers: +4% at 8192^3, -9% on the 16x16 convs, 2-3x slower wherever the spilling epilogue matters).
-  switch (cfg) {
-    case 1: return launch_cfg<T, MODE, 128, 128, 2, 2, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-    case 3: return launch_cfg<T, MODE, 128, 64, 2, 2, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-    case 6: return launch_cfg<T, MODE, 256, 128, 4, 2, 3>(ad, W, bsw, ep, M, N, K, batch, s);
-    case 9: return launch_cfg<T, MODE, 256, 256, 2, 4, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-    case 12: return launch_cfg<T, MODE, 128, 320, 4, 2, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-    default: return launch_cfg<T, MODE, 128, 128, 2, 2, 2>(ad, W, bsw, ep, M, N, K, batch, s);
-  }
-#endif
 }
 
 int epi_fast(const Epi& ep, int N, int n_out, int esz) {
@@ -978,7 +878,7 @@ extern "C" int mmgt_tune(const char* key, int value) {
   if (key)
     for (HostSwitch& h : g_host)
       if (!strcmp(key, h.key)) { h.value = value; return 0; }
-  if (key && !strcmp(key, "gemm_cfg")) { g_gemm_cfg = value; return 0; }
+  if (key && !strcmp(key, "gemm_cfg")) { g_sw.gemm_cfg = value; return 0; }
   if (key && !strcmp(key, "attn64")) { mmgt_attn_set64(value); return 0; }
   if (key && !strcmp(key, "attn_nomax") && (value == 0 || value == 1)) { mmgt_attn_set_nomax(value); return 0; }
   if (key && !strcmp(key, "attn_heads_inner")) { mmgt_attn_set_heads_inner(value); return 0; }
@@ -990,9 +890,9 @@ extern "C" int mmgt_tune(const char* key, int value) {
   if (key && !strcmp(key, "gn_narrow")) { mmgt_gn_set_narrow(value); return 0; }
   if (key && !strcmp(key, "gn_slab")) { mmgt_gn_set_slab(value); return 0; }
   if (key && !strcmp(key, "gn_lpr0")) { if (value != 4 && value != 8 && value != 16) return -1; mmgt_gn_set_lpr0(value); return 0; }
-  if (key && !strcmp(key, "splitk")) { g_splitk = value; return 0; }
-  if (key && !strcmp(key, "bm192")) { g_bm192 = value; return 0; }
-  if (key && !strcmp(key, "tailsplit")) { g_tailsplit = value; return 0; }
+  if (key && !strcmp(key, "splitk")) { g_sw.splitk = value; return 0; }
+  if (key && !strcmp(key, "bm192")) { g_sw.bm192 = value; return 0; }
+  if (key && !strcmp(key, "tailsplit")) { g_sw.tailsplit = value; return 0; }
   if (key && !strcmp(key, "rconv_cb") && (value == 0 || value == 320 || value == 256 || value == 160)) { mmgt_rconv_set_cb(value); return 0; }
   if (key && !strcmp(key, "rconv_stagger") && value >= 0 && value <= 8192) { mmgt_rconv_set_stagger(value); return 0; }
 #ifdef MMGT_ABLATE   // libmmgt_hip_abl.so (`make abl`): timing ablations whose RESULTS ARE GARBAGE -- the instruments under tools/ load that library explicitly

@@ -739,12 +739,12 @@ extern "C" int mmgt_gemm_bf16_f32(const void* A, long lda, const void* W, long l
 
 // Entry for gemm.hip's dispatcher.  Preconditions (checked there): bf16, vectorised epilogue (ep.fast), act in {none, GEGLU}
 // (GEGLU with bn = 256 only and without row scale / alpha / post-scale bias), 16-byte aligned bias vectors, K % 64 == 0.
-int mmgt_gemm16_launch(int mode, int bn, const void* adp, const void* W, long bsw, const void* epp, int M, int N, int K,
+int mmgt_gemm16_launch(int mode, int bm, int bn, const void* adp, const void* W, long bsw, const void* epp, int M, int N, int K,
                        int batch, void* stream) {
   const ADesc& ad = *reinterpret_cast<const ADesc*>(adp);
   const Epi& ep = *reinterpret_cast<const Epi*>(epp);
   hipStream_t s = (hipStream_t)stream;
-  if (bn == 192320) return mode == 0 ? launch16<0, 320, 192>(ad, W, bsw, ep, M, N, K, batch, s) : launch16<1, 320, 192>(ad, W, bsw, ep, M, N, K, batch, s);   // 192 x 320 tile
+  if (bm == 192) return mode == 0 ? launch16<0, 320, 192>(ad, W, bsw, ep, M, N, K, batch, s) : launch16<1, 320, 192>(ad, W, bsw, ep, M, N, K, batch, s);   // 192 x 320 tile (the only 192-row one)
   if (bn == 320) return mode == 0 ? launch16<0, 320>(ad, W, bsw, ep, M, N, K, batch, s) : launch16<1, 320>(ad, W, bsw, ep, M, N, K, batch, s);
   if (bn == 128) return mode == 0 ? launch16<0, 128>(ad, W, bsw, ep, M, N, K, batch, s) : launch16<1, 128>(ad, W, bsw, ep, M, N, K, batch, s);   // 256 x 128 tile (the VAE's 128-wide levels)
   return mode == 0 ? launch16<0, 256>(ad, W, bsw, ep, M, N, K, batch, s) : launch16<1, 256>(ad, W, bsw, ep, M, N, K, batch, s);

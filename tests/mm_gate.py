@@ -32,7 +32,7 @@ LINEAR  (gemm, gemm_post, batched, conv1x1_cat, GEGLU; the convs reduce to it ov
   with s = row_scale * alpha, d_h / d_g the bracket of the h / g column.
 
 CONV  (conv3x3: stride 1, 2, -2 = pad-high-only, upsample True and 2, two sources; conv1x1_cat is LINEAR over [x0 | x1])
-  gemm.hip:1108-1152 builds the implicit GEMM: rows (n, y, x), reduction (ky, kx, cin) over x0 | x1, zero padding by out-of-range DMA offsets
+  gemm.hip:1008-1052 builds the implicit GEMM: rows (n, y, x), reduction (ky, kx, cin) over x0 | x1, zero padding by out-of-range DMA offsets
   (gemm_common.h:51-53), then the LINEAR epilogue with bias2_rows counted in output pixels.  Contract and bound are the LINEAR ones over the
   gathered reduction of 9 Cin (4 Cin for the four-phase form).
   Folded weights (packing.pack_conv3x3_up2: the taps that fall on one stored pixel summed in fp32 and rounded once; the [W_po W2 | W_po] image of

@@ -4,7 +4,8 @@ computed with torch on the device.  Operands are views with NaN rows (and column
 that must come back untouched, every `hip.tune` is restored in a `finally`.  tests/test_mm_gate.py proves on the CPU that this gate rejects subtly
 wrong kernels which the flat tolerance of tests/test_hip_kernels.py accepts.
 
-Which branch a case reaches is read from the dispatchers (csrc/gemm.hip `launch`, `epi_fast`, `gemm_entry`; csrc/norm.hip): a forced `gemm_cfg`
+Which branch a case reaches is read from the dispatchers (csrc/gemm_plan.h `plan_gemm`, which tests/test_gemm_plan.py checks on the CPU; csrc/gemm.hip
+`epi_fast`, `gemm_entry`; csrc/norm.hip): a forced `gemm_cfg`
 runs that tile unless the epilogue needs another instantiation -- cfg 16 / 17 / 19 / 20 are bf16 only and take no activation (GEGLU: cfg 16) and
 fall back to cfg 9 / 12 / 12 / 1; an activation other than GEGLU, a problem that is not `fast` (N % 8, 16-byte rows, bias2_rows >= 256) runs the
 FULL 128 x 128 instantiation; row scale / alpha / bias_post run its EPI = 1 form (gemm16: its POST epilogue).  The entry points do not tell the
@@ -90,8 +91,8 @@ def run_linear(c, cfg=0, ld=None, col0=0):
 def test_gemm_every_tile_configuration(M, N, K, epi, dt):
     """Forced cfg 1, 3, 6, 9, 12 (32x32 MFMA tiles, both dtypes), 16, 17, 19, 20 (gemm16, bf16; others fall back as the module docstring says)
     and the heuristic's choice.  `post` is mmgt_gemm_post on a strided A view with alpha = 0.75; GEGLU takes pack_geglu's image (N = 2 x the
-    output width, a multiple of 64) and reaches its own epilogue on cfg 1, 6, 9, 16 and through the dispatcher's fallback (cfg 3, 12 -> 1,
-    gemm.hip:814; 17, 19 -> 1, :871; 20 -> 1, :876) on the others."""
+    output width, a multiple of 64) and reaches its own epilogue on cfg 1, 6, 9, 16 and through the planner's fallback (cfg 3, 12 -> 1; 17, 19 -> 1;
+    20 -> 1: the GEGLU and gemm16 rules of gemm_plan.h `plan_gemm`) on the others."""
     if epi == "geglu":
         N = 2 * (N // 32 * 32)
     c = linear(epi, M, N, K, dt)
@@ -102,8 +103,8 @@ def test_gemm_every_tile_configuration(M, N, K, epi, dt):
 @pytest.mark.parametrize("dt", DT, ids=["bf16", "f32"])
 @pytest.mark.parametrize("how", ["bias2_rows = 7", "N = 1282", "8-byte rows"])
 def test_gemm_full_instantiation_three_ways(how, dt):
-    """`epi_fast` (gemm.hip:910-916) is false -- bias2 blocks shorter than a tile, N % 8 != 0, output rows 8-byte but not 16-byte aligned -- so
-    every cfg runs the element-wise epilogue of the FULL 128 x 128 instantiation (gemm.hip:879, :667-702)."""
+    """`epi_fast` (gemm.hip:810-816) is false -- bias2 blocks shorter than a tile, N % 8 != 0, output rows 8-byte but not 16-byte aligned -- so
+    every cfg runs the element-wise epilogue of the FULL 128 x 128 instantiation (gemm_plan.h `plan_gemm`: T128x128_FULL; gemm.hip:667-702)."""
     esz = 2 if dt == BF16 else 4
     if how == "bias2_rows = 7":
         c, ld = G.linear_case("full.b2", 300, 320, 192, dt=dt, device=DEV, guard=True, bias=True, bias2_rows=7, residual=True), None
@@ -119,14 +120,14 @@ def test_gemm_full_instantiation_three_ways(how, dt):
 @pytest.mark.parametrize("dt", DT, ids=["bf16", "f32"])
 @pytest.mark.parametrize("M,N,K,act", [(1, 1280, 320, "silu"), (1, 1282, 320, "none"), (1, 1280, 1280, "none"), (2, 1282, 320, "none"), (4, 640, 64, "silu")])
 def test_gemm_of_a_few_rows(M, N, K, act, dt):
-    """M = 1 without bias2 / scale / residual runs gemv_kernel (gemm.hip:1066), M = 2 and 4 stay on the tiles (SiLU, N % 8 != 0: FULL)."""
+    """M = 1 without bias2 / scale / residual runs gemv_kernel (gemm.hip:966), M = 2 and 4 stay on the tiles (SiLU, N % 8 != 0: FULL)."""
     c = G.linear_case("few", M, N, K, dt=dt, device=DEV, guard=True, bias=True, act=act, wscale=2.0 if act == "silu" else 1.0)
     gate(run_linear(c), c, f"{c.what} {act}")
 
 
 @pytest.mark.parametrize("K,split", [(2560, True), (2496, False)])
 def test_gemm_either_side_of_the_split_k_condition(K, split):
-    """gemm.hip:757-771: bf16, plain vectorised epilogue, K >= 2560, N % 256 == 0; one tile, K / 64 = 40 chunks -> S = 2 slices of 20 >= 16
+    """gemm_plan.h `plan_gemm` / `splitk_slices`: bf16, plain vectorised epilogue, K >= 2560, N % 256 == 0; one tile, K / 64 = 40 chunks -> S = 2 slices of 20 >= 16
     chunks; K = 2496 is below the condition and runs one launch.  As tests/test_step_shapes_gpu.py does, the `splitk` switch tells the two apart:
     with it off the split shape runs the unsplit kernel, whose result it must match to the gate, and the plain shape must not change at all."""
     from mmgt_amd import hip
@@ -227,7 +228,7 @@ CONV_CASES = [(c0, c1, cout, H, W, mode, dt) for c0, c1, cout in [(64, 0, 320), 
 @pytest.mark.parametrize("c0,c1,cout,H,W,mode,dt", CONV_CASES, ids=[f"{c[0]}+{c[1]}-{c[2]}-{c[3]}x{c[4]}-{c[5]}-{str(c[6])[6:]}" for c in CONV_CASES])
 def test_conv3x3_gather_modes(c0, c1, cout, H, W, mode, dt):
     """mmgt_conv3x3_nhwc: stride 1, 2, -2 (zero padding behind the last row / column only), the 3 x 3 conv on the nearest-2x view (`up`) and
-    its four-phase form (`up2`: bf16, one source, gemm16 only -- gemm.hip:815 sends every other cfg there), one and two sources (the seam inside a
+    its four-phase form (`up2`: bf16, one source, gemm16 only -- gemm_plan.h `plan_gemm` sends every other cfg there), one and two sources (the seam inside a
     64-channel chunk run: 320 | 128), 8 images (280 / 512 / 8 output rows before striding: more than one row tile at 5 x 7 and 8 x 8), forced
     cfg 1, 3, 12, 16, 17 (fp32: 16 / 17 fall back to 9 / 12) and the heuristic's."""
     c = G.conv_case(f"cv.{mode}", 8, H, W, c0, cout, c1, dt=dt, device=DEV, guard=True, **MODES[mode])
@@ -240,7 +241,7 @@ def test_conv3x3_gather_modes(c0, c1, cout, H, W, mode, dt):
 @pytest.mark.parametrize("b2rows", [256, 64])
 def test_conv3x3_bias2_and_residual_on_both_epilogues(b2rows, dt):
     """bias2 + residual on the conv path: bias2_rows = 256 (four 8 x 8 images per row) keeps `epi_fast` and runs the vectorised epilogue of
-    every tile, 64 (one image per row) is below a tile's rows and runs the FULL instantiation (gemm.hip:913, :879)."""
+    every tile, 64 (one image per row) is below a tile's rows and runs the FULL instantiation (gemm.hip:813; gemm_plan.h `plan_gemm`)."""
     c = G.conv_case("cv.b2", 8, 8, 8, 64, 320, dt=dt, device=DEV, guard=True, bias2_rows=b2rows, residual=True)
     for cfg in CONV_CFG:
         gate(run_conv(c, cfg), c, f"{c.what} bias2_rows {b2rows} cfg {cfg}")
