@@ -683,6 +683,19 @@ int mmgt_vp8dec_output(const long long* tab, unsigned int* scratch, long long sc
  * masks (frames, 512, 512) u8 (face = face box + hand boxes with the reference's uint8 wrap-around).  H = W = 512 (the reference's canvas). */
 int mmgt_dwpose_draw(const float* kp, unsigned char* pose, unsigned char* hands_mask, unsigned char* lips_mask, unsigned char* face_mask,
                      int frames, int H, int W, void* stream);
+/* ---- Audio input (csrc/audio.hip, csrc/audio_core.h, mmgt_amd/audio_in.py): what librosa.load(path, sr=16000) does for the reference
+ * (data/audio_extraction/wavlm_features.py:61,128, src/dataset/audio_processor.py:106,142) on a WAV file's `data` chunk that is already on the
+ * device.  Every buffer is a device pointer.
+ * decode_mono: raw = n_frames interleaved little-endian frames of `channels` (1 .. 16) samples of format fmt (audio_core.h: 0 U8, 1 S16, 2 S24,
+ * 3 S32, 4 F32, 5 F64) at ANY byte address -> out (n_frames,) fp32 in [-1, 1): the channels summed in fp32 in channel order, one division by the
+ * channel count, full scale a power of two (U8 and S16 sum the raw integers and scale last; the other formats scale first).  Reads exactly
+ * n_frames * channels * sample bytes, writes exactly n_frames floats. */
+int mmgt_audio_decode_mono(const unsigned char* raw, float* out, long long n_frames, int channels, int fmt, void* stream);
+/* resample: y[j] = sum_i x[i] h[j down - i up + half] for j < n_out = ceil(n_in up / down), zeros beyond both ends of x; up != down, reduced by
+ * their gcd; h = 2 half + 1 taps on the up-sampled grid, handed over phase-major as `taps`: up rows of 2 half / up + 1 floats, row p =
+ * h[p], h[p + up], ..., zero where the index passes 2 half.  One fp32 fma chain per output in ascending tap order; no atomics: the result does not
+ * depend on the grid.  A workgroup's input span must fit 64 KiB of LDS (ratios up to 16 with the Kaiser-best filter do); n_in below 2^31. */
+int mmgt_audio_resample(const float* x, long long n_in, const float* taps, int up, int down, int half, float* y, long long n_out, void* stream);
 
 #ifdef __cplusplus
 }

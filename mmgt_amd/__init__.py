@@ -20,4 +20,7 @@ def __getattr__(name):
     if name in ("pose_tensor_device", "motion_masks_device", "resize_frames_device", "ref_image_tensors_device"):
         from . import inputs
         return getattr(inputs, name)
+    if name in ("parse_wav", "WavInfo", "resample_plan", "resample_device", "read_audio_device"):
+        from . import audio_in
+        return getattr(audio_in, name)
     raise AttributeError(f"module 'mmgt_amd' has no attribute {name!r}")

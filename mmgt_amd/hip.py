@@ -169,6 +169,8 @@ _SIGS = {
     "mmgt_vp8dec_filter": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_int, c_void_p]),
     "mmgt_vp8dec_output": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, c_int, ctypes.c_longlong, c_void_p]),
     "mmgt_dwpose_draw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mmgt_audio_decode_mono": (c_int, [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p]),
+    "mmgt_audio_resample": (c_int, [c_void_p, ctypes.c_longlong, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_longlong, c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS)
@@ -2112,3 +2114,40 @@ def dwpose_draw(kp, H=512, W=512):
     hands, lips, face = (torch.empty((L, H, W), device=kp.device, dtype=torch.uint8) for _ in range(3))
     _check(lib().mmgt_dwpose_draw(_ptr(kp), _ptr(pose), _ptr(hands), _ptr(lips), _ptr(face), L, H, W, _stream()), "mmgt_dwpose_draw")
     return pose, hands, lips, face
+
+
+# ----------------------------------------------------------------------------------------------------- audio input
+
+AUDIO_SAMPLE_BYTES = (1, 2, 3, 4, 4, 8)          # csrc/audio_core.h: U8, S16, S24, S32, F32, F64
+
+
+def audio_decode_mono(raw, n_frames, channels, fmt, out=None):
+    """The interleaved little-endian frames at the start of raw uint8 (bytes,) -- a view at any byte offset will do -- as (n_frames,) fp32 mono
+    (include/mmgt_hip.h: mmgt_audio_decode_mono).  `out`: the tensor to write into."""
+    _dev(raw, out)
+    need = int(n_frames) * int(channels) * AUDIO_SAMPLE_BYTES[fmt] if 0 <= fmt < 6 else 0
+    if raw.dtype != torch.uint8 or raw.dim() != 1 or not raw.is_contiguous() or raw.numel() < need:
+        raise RuntimeError(f"audio_decode_mono: expected raw uint8 (bytes,), contiguous, of at least {need} bytes")
+    if out is None:
+        out = torch.empty((int(n_frames),), device=raw.device, dtype=torch.float32)
+    if _f32(out, "audio_decode_mono: out").shape != (int(n_frames),):
+        raise RuntimeError(f"audio_decode_mono: out must hold ({int(n_frames)},) floats")
+    _check(lib().mmgt_audio_decode_mono(_ptr(raw), _ptr(out), int(n_frames), int(channels), int(fmt), _stream()), "mmgt_audio_decode_mono")
+    return out
+
+
+def audio_resample(x, taps, up, down, half, out=None):
+    """x (n_in,) fp32 through the polyphase FIR whose phase-major table is taps (up * (2 * half // up + 1),) fp32 -> (ceil(n_in * up / down),) fp32
+    (include/mmgt_hip.h: mmgt_audio_resample).  `out`: the tensor to write into."""
+    _dev(x, taps, out)
+    _f32(x, "audio_resample: x"), _f32(taps, "audio_resample: taps")
+    n_in = x.numel()
+    n_out = -(-n_in * int(up) // int(down))
+    if x.dim() != 1 or taps.dim() != 1 or taps.numel() != int(up) * (2 * int(half) // int(up) + 1):
+        raise RuntimeError(f"audio_resample: x must be 1-D and taps hold up * (2 * half // up + 1) = {int(up) * (2 * int(half) // int(up) + 1)} floats")
+    if out is None:
+        out = torch.empty((n_out,), device=x.device, dtype=torch.float32)
+    if _f32(out, "audio_resample: out").shape != (n_out,):
+        raise RuntimeError(f"audio_resample: out must hold ({n_out},) floats")
+    _check(lib().mmgt_audio_resample(_ptr(x), n_in, _ptr(taps), int(up), int(down), int(half), _ptr(out), n_out, _stream()), "mmgt_audio_resample")
+    return out

@@ -4,6 +4,7 @@
 
     python scripts/audio2vid.py --synthetic -W 512 -H 512 -L 24 --steps 25
     python scripts/audio2vid.py --synthetic -L 24 --init_video clip.npy --regen_mask lips --paste_back    # dub an existing clip
+    python scripts/audio2vid.py --synthetic --audio_path talk_48k.wav --audio_decoder device              # any PCM / float WAV, any rate
 
 The chain is the reference's (line numbers of its scripts/audio2vid.py):
   1. Stage-1 SMGA (:198-200,324-348): one guided 50-step DDIM sample of 80 key-point frames per 3.2-second audio slice, each slice
@@ -83,6 +84,9 @@ def parse_args():
     p.add_argument("--gif_delta", action="store_true",
                    help="with --gif_encoder device: frame differencing, a pixel that keeps its palette index from one frame to the next is written "
                         "as the transparent index 255 (a palette of 255 colours)")
+    p.add_argument("--audio_decoder", default="wave", choices=["wave", "device"],
+                   help="reader of --audio_path: wave (stdlib, 16-kHz 16-bit PCM only) or device (mmgt_amd.audio_in, DESIGN 4r: any PCM / float "
+                        "WAV, 8 .. 64 bits, 1 .. 16 channels, any rate, decoded, mixed down and resampled to 16 kHz on the GPU)")
     p.add_argument("--wavlm", default="off", metavar="{off,random,PATH}",
                    help="WavLM-Large features of --audio_path as columns 0:1024 of the SMGA conditioning: off (hash-seeded stand-in, the default), "
                         "random (hash-seeded Large weights) or the path of a WavLM-Large.pt checkpoint")
@@ -140,7 +144,8 @@ def read_wav_16k(path):
     import wave
     with wave.open(path, "rb") as w:
         if w.getframerate() != 16000:
-            raise SystemExit(f"audio2vid: {path} is sampled at {w.getframerate()} Hz; resample to 16 kHz first (librosa is not part of this build)")
+            raise SystemExit(f"audio2vid: {path} is sampled at {w.getframerate()} Hz; resample to 16 kHz first (librosa is not part of this build), "
+                             "or pass --audio_decoder device")
         if w.getsampwidth() != 2:
             raise SystemExit(f"audio2vid: {path} must be 16-bit PCM")
         pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").reshape(-1, w.getnchannels())
@@ -173,6 +178,19 @@ def main():
     dev = torch.device("cuda:0")
     dtype = torch.bfloat16 if a.dtype == "bf16" else torch.float32
     timing = {}
+    if a.audio_decoder == "device":                         # any PCM / float WAV: decode, down-mix and resampling on the device
+        from mmgt_amd.audio_in import FORMAT_NAMES, parse_wav, pcm16_host, read_audio_device
+        if not a.audio_path:
+            raise SystemExit("audio2vid: --audio_decoder device goes with --audio_path")
+        try:
+            wav_info = parse_wav(a.audio_path)
+        except ValueError as e:
+            raise SystemExit(f"audio2vid: {e}")
+        import functools
+        read_wave = functools.lru_cache(None)(lambda path: read_audio_device(path, device=dev))      # both consumers share one decode; it stays on the device
+        read_pcm = pcm16_host
+    else:
+        read_wave, read_pcm = read_wav_16k, read_wav_pcm
     t0 = time.time()
     from mmgt_amd.smga import smga_spec
     keys = smga_spec(cond_feature_dim=1059 if a.feature_type == "wavlm" else 35)
@@ -196,7 +214,7 @@ def main():
             raise SystemExit("audio2vid: --wavlm needs --audio_path (a 16-kHz PCM .wav)")
         torch.cuda.synchronize()
         t0 = time.time()
-        slices = audio_slices(read_wav_16k(a.audio_path))
+        slices = audio_slices(read_wave(a.audio_path))
         if slices.shape[0] < n_slices or slices.shape[1] != 51200:
             raise SystemExit(f"audio2vid: {a.audio_path} gives {slices.shape[0]} slice(s) of {slices.shape[1]} samples; -L {a.L} needs "
                              f"{n_slices} full 3.2-s slices (the reference skips the first window of clips longer than 3.3 s)")
@@ -252,7 +270,11 @@ def main():
     w2v = Wav2VecModel(device=dev, dtype=dtype)
     w2v.load_state_dict(synth_state_dict(wav2vec_spec(), prefix="w2v.", device=dev))
     if a.audio_path:      # a 16-kHz PCM .wav drives the Stage-2 audio conditioning (audio_processor.py:103-110 loads with librosa at 16 kHz)
-        wave = read_wav_16k(a.audio_path)[None, :a.L * 16000 // (a.fps or 25)]
+        wave = read_wave(a.audio_path)
+        if a.audio_decoder == "device":
+            extra["audio"] = {"rate": wav_info.rate, "channels": wav_info.channels, "fmt": FORMAT_NAMES[wav_info.fmt],
+                              "samples_16k": int(wave.shape[0])}
+        wave = wave[None, :a.L * 16000 // (a.fps or 25)]
     else:
         wave = hash_uniform("a2v.wave", (1, a.L * 16000 // (a.fps or 25)), 1.0)
     wave = ((wave - wave.mean()) / (wave.var(unbiased=False) + 1e-7).sqrt()).to(dev)                        # Wav2Vec2FeatureExtractor's normalisation
@@ -300,7 +322,7 @@ def main():
         fps = a.fps or 25
         t0 = time.time()
         jpegs = encode_jpeg_frames(v[0], a.quality)
-        sound = read_wav_pcm(a.audio_path, a.L / fps) if a.audio_path else None
+        sound = read_pcm(a.audio_path, a.L / fps) if a.audio_path else None
         extra["bytes"] = write_avi(path, jpegs, a.W, a.H, fps, audio=sound)
         extra["encode_s"] = round(time.time() - t0, 3)
     elif a.format == "pngs":                               # a directory that `ffmpeg -i %04d.png` reads
